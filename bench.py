@@ -16,6 +16,13 @@ the same way.  So the driver's 1 -> 8 curve compares one workload.  BASELINE
 configs[3] (2^28 preloaded keys per GPU, mixed 50/50,
 routed) is its own line: --config 4.
 
+A plain config-2 run does only what the headline needs: set-up, warm-up, the
+timed steps, the result line.  --full adds what takes runs of its own: the
+check of every result, one more step under HIP events (per-class kernel
+times), the lines-per-Get count, the measured random-access ceilings and the
+roofline built on them, and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step returned (dump_outputs).
+
 Prints ONE JSON line on rank 0 (stdout); diagnostics go to stderr.
 """
 from __future__ import annotations
@@ -53,6 +60,12 @@ def parse():
     ap.add_argument("--keys", type=int, default=1 << 26, help="keys per GPU")
     ap.add_argument("--batch", type=int, default=1 << 20)
     ap.add_argument("--init-cap", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="config 2: after the timed steps also check every result, run one step under HIP events "
+                         "(kernel_ms_per_step), count the lines per Get, measure the random-access ceilings "
+                         "(roofline) and time the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 2: write what the last timed step returned as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=1 << 23,
                     help="keys of the CPU baseline thread sweep (1/8 of config 2, same load trajectory)")
@@ -74,7 +87,12 @@ def parse():
     ap.add_argument("--route", action="store_true",
                     help="one GPU: run the N>1 routed path anyway (pack, RCCL all-to-all over a "
                          "1-rank group, unpack) to measure its cost")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.config or 2) != 2:
+        ap.error("--dump-outputs is implemented for config 2")
+    return a
 
 
 def spawn_ranks(a) -> int:
@@ -120,6 +138,38 @@ def emit(res):
         sys.stdout.flush()
     else:
         os.write(_JSON_FD, line)
+
+
+DUMP_SAMPLE = 1 << 20  # ops of the seeded sample (five arrays, 32 MB in all)
+
+
+def dump_outputs(dirname, st_ins, v_get, s_get, nb):
+    """--dump-outputs DIR: what the last timed step of config 2 returned -- the
+    status of every Insert, the value and the status of every Get, in op
+    order -- as .npy files two builds can be compared by:
+      sample_index            the ops sampled (DUMP_SAMPLE of them, a fixed
+                              seeded draw; every op when there are no more)
+      insert_status, get_status          float32, at the sampled ops
+      get_value_hi32, get_value_lo32     float64, the halves of the sampled
+                                         64-bit values (each exact)
+      *_batch_sum             float64 [batches]: the same four quantities
+                              summed over every op of each batch (integer
+                              sums, exact up to 2^21 ops per batch)
+    The inputs are seeded (gen_keys), so the files of two runs with the same
+    arguments are equal element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    n = st_ins.numel()
+    pick = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(20260).integers(0, n, DUMP_SAMPLE))
+    d_pick = torch.from_numpy(pick).to(st_ins.device)
+    hi, lo = (v_get >> 32) & 0xFFFFFFFF, v_get & 0xFFFFFFFF
+    out = {"sample_index": pick.astype(np.float64)}
+    for name, t, dt in (("insert_status", st_ins, np.float32), ("get_status", s_get, np.float32),
+                        ("get_value_hi32", hi, np.float64), ("get_value_lo32", lo, np.float64)):
+        out[name] = t[d_pick].cpu().numpy().astype(dt)
+        out[name + "_batch_sum"] = t.view(nb, -1).sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+    log(f"dump-outputs: {len(out)} arrays, {sum(x.nbytes for x in out.values()) / 1e6:.1f} MB -> {dirname}")
 
 
 def main():
@@ -219,7 +269,7 @@ def config2(a):
         step(pipelined)
     # the timed steps run without HIP events: an event at every kernel-class
     # boundary (6 per insert batch) costs ~6 % of the step; the per-class
-    # kernel times come from one more, identical step with events (below)
+    # kernel times come from one more, identical step with events (--full, below)
     idx.timing(events=False)
     if routed:
         dist.barrier()
@@ -231,40 +281,16 @@ def config2(a):
     if routed:
         dist.barrier()
     t1 = time.perf_counter()
-    idx.timing(events=True)
-    idx.timing_read(reset=True)
-    # the measured kernel durations (HIP events on the engine stream), batch by
-    # batch so no class overlaps another (the pipelined steps overlap each
-    # batch's k_part with the previous batch's apply chain)
-    step(False)
-    torch.cuda.synchronize()
-    idx.timing(events=False)
-    kt = idx.timing_read(reset=True)
     el = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if routed:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
-
-    # correctness of the last step (outside the timed region)
-    bad = 0
-    for i in range(nb):
-        bad += int((st_ins[i] != P.ST_INSERTED).sum())
-        v, s = out_get[i]
-        bad += int(((s != P.ST_HIT) | (v != keys[i])).sum())
-    stats = idx.stats()
-
-    # lines per Get on the final table (instrumented k_get, not timed)
-    idx.timing(events=False, count_lines=True)
-    lines_per_get = None
-    if world == 1:
-        idx.Get(keys[nb // 2])
-        torch.cuda.synchronize()
-        lines_per_get = idx.last_get_lines() / B
-    idx.timing(events=False, count_lines=False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, torch.cat(st_ins), torch.cat([o[0] for o in out_get]),
+                     torch.cat([o[1] for o in out_get]), nb)
 
     ops_total = 2 * NK * world * a.steps
     value = ops_total / elapsed / 1e6
-    cls = {k: {"ms": v[0], "launches": v[1]} for k, v in kt.items() if v[1]}  # one step
     wl = ("config2: per GPU 64M unique uniform u64 keys (value=key), CCEH_hybrid(65536); "
           "64 Insert batches of 1M then 64 Get batches of 1M (100% hit); index reset each step")
     if a.upsert:
@@ -295,19 +321,48 @@ def config2(a):
             "keys_per_gpu": NK, "batch": B, "init_cap": a.init_cap,
             "parallelism": f"hash-prefix shards x{world}" + (", RCCL all-to-all routing (fixed-capacity owner blocks)" if routed else ""),
         },
-        "correct": bad == 0,
-        "index": {"depth": stats["depth"], "segments": stats["segments"], "splits_per_step": stats["splits"],
-                  "insert_passes_per_step": stats["insert_passes"] / max(1, stats["batches"]) if stats["batches"] else None,
-                  "fast_declined_buckets": stats.get("fast_declined")},
-        "kernel_ms_per_step": {k: round(v["ms"], 3) for k, v in cls.items()},
     }
-    if rank == 0 and world == 1:
-        ceil = gather_ceiling(dev)
-        res["roofline"] = roofline(cls, lines_per_get, B, nb, NK, stats, a.steps, ceil,
-                                   ms_per_step=round(elapsed / a.steps * 1e3, 3))
-        res["get_mops"] = round(NK / (cls["get"]["ms"] / 1e3) / 1e6, 1) if "get" in cls else None
-        if not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(a)
+    if a.full:
+        # the measured kernel durations (HIP events on the engine stream), batch by
+        # batch so no class overlaps another (the pipelined steps overlap each
+        # batch's k_part with the previous batch's apply chain)
+        idx.timing(events=True)
+        idx.timing_read(reset=True)
+        step(False)
+        torch.cuda.synchronize()
+        idx.timing(events=False)
+        kt = idx.timing_read(reset=True)
+
+        # correctness of the last step (outside the timed region)
+        bad = 0
+        for i in range(nb):
+            bad += int((st_ins[i] != P.ST_INSERTED).sum())
+            v, s = out_get[i]
+            bad += int(((s != P.ST_HIT) | (v != keys[i])).sum())
+        stats = idx.stats()
+
+        # lines per Get on the final table (instrumented k_get, not timed)
+        idx.timing(events=False, count_lines=True)
+        lines_per_get = None
+        if world == 1:
+            idx.Get(keys[nb // 2])
+            torch.cuda.synchronize()
+            lines_per_get = idx.last_get_lines() / B
+        idx.timing(events=False, count_lines=False)
+
+        cls = {k: {"ms": v[0], "launches": v[1]} for k, v in kt.items() if v[1]}  # one step
+        res["correct"] = bad == 0
+        res["index"] = {"depth": stats["depth"], "segments": stats["segments"], "splits_per_step": stats["splits"],
+                        "insert_passes_per_step": stats["insert_passes"] / max(1, stats["batches"]) if stats["batches"] else None,
+                        "fast_declined_buckets": stats.get("fast_declined")}
+        res["kernel_ms_per_step"] = {k: round(v["ms"], 3) for k, v in cls.items()}
+        if rank == 0 and world == 1:
+            ceil = gather_ceiling(dev)
+            res["roofline"] = roofline(cls, lines_per_get, B, nb, NK, stats, a.steps, ceil,
+                                       ms_per_step=round(elapsed / a.steps * 1e3, 3))
+            res["get_mops"] = round(NK / (cls["get"]["ms"] / 1e3) / 1e6, 1) if "get" in cls else None
+            if not a.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(a)
     if rank == 0:
         emit(res)
     if routed:

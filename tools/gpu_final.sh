@@ -17,14 +17,14 @@ a)
 b)
   O=gpurun_out/ev_$R
   mkdir -p $O
-  timeout -k 10 600 python -u bench.py > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
+  timeout -k 10 600 python -u bench.py --full > $O/bench_config2.json 2> $O/bench_config2.err || exit 1
   echo config2 done
   for c in "--config 2 --upsert --no-cpu-baseline" "--config 2 --route --no-cpu-baseline" "--config 3 --no-cpu-baseline" \
            "--config 4 --no-cpu-baseline" "--config 4 --route --no-cpu-baseline" "--config 5 --no-cpu-baseline" \
            "--config 6 --no-cpu-baseline" "--config 7 --no-cpu-baseline" "--config 8 --steps 2" \
            "--config 2 --init-cap 2 --no-cpu-baseline"; do
     tag=$(echo "$c" | tr -dc 'a-z0-9')
-    timeout -k 10 600 python -u bench.py $c > $O/bench_$tag.json 2> $O/bench_$tag.err || { echo "failed: $c"; exit 1; }
+    timeout -k 10 600 python -u bench.py --full $c > $O/bench_$tag.json 2> $O/bench_$tag.err || { echo "failed: $c"; exit 1; }
     echo "$c done"
   done
   ;;

@@ -3,7 +3,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/sqa
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pipeline"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-pipeline"
 R="k_apply|k_part|k_split"
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT -T -f csv --kernel-include-regex "$R" -d gpurun_out/sqa/p1 -o run -- $B > /dev/null 2> gpurun_out/sqa/p1.err
 echo p1 $?

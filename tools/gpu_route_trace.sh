@@ -3,7 +3,8 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/rtr
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/rtr -o run -- python3 bench.py --route --steps 2 --warmup 1 --no-cpu-baseline > gpurun_out/rtr/bench.json 2> gpurun_out/rtr/bench.err || exit 1
-f=$(find gpurun_out/rtr -name 'run_kernel_trace.csv' | head -1)
-python3 tools/trace_busy.py "$f" --from-kernel k_init_segments > gpurun_out/rtr/busy.txt && cat gpurun_out/rtr/busy.txt
+O=${OUT_DIR:-bench_out}/rtr
+mkdir -p $O
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O -o run -- python3 bench.py --full --route --steps 2 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit 1
+f=$(find $O -name 'run_kernel_trace.csv' | head -1)
+python3 tools/trace_busy.py "$f" --from-kernel k_init_segments > $O/busy.txt && cat $O/busy.txt

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 R=${1:-r03}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
-B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline"
+B="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-pipeline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -f csv -d $OUT/trace -o run -- $B > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace done"
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE -T -f csv -d $OUT/pmc_fetch -o run -- $B > $OUT/pmc_fetch.json 2> $OUT/pmc_fetch.err
