@@ -39,6 +39,7 @@
 
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "knobs.h"
 
 namespace pmdfc {
 
@@ -65,39 +66,6 @@ __device__ __forceinline__ uint32_t sk_item(uint64_t k) { return (uint32_t)(k >>
 __device__ __forceinline__ uint32_t sk_home(uint64_t k) { return (uint32_t)k & 0xFFu; }
 
 // --------------------------------------------------------------- partition
-
-struct PartArgs {
-  const uint64_t* keys;
-  const uint64_t* vin;
-  const uint8_t* ops;   // null: insert-only batch (k_part resolves statuses itself)
-  uint8_t* st;
-  uint64_t n;
-  uint32_t kvs;         // u64 words from one op's key (value) to the next: 1, or 2 for {key, value} records
-  uint32_t sbits, shard, p1, sbb;  // p1: partition bucket bits; sbb: sub-bucket bits
-  uint32_t cap;         // record slots per bucket region
-  uint32_t capx;        // ... per sub-region (cap / kPartSubs)
-  uint64_t ovf_base;    // first overflow record slot
-  ulonglong2* rkv;      // records: {key, value}
-  uint32_t* rop;        // records: op index | sub-bucket << 22 | Get << 31
-  uint16_t* robk;       // bucket of each overflow record
-  uint32_t* cursor;     // this batch's cursors, [sub-region][bucket] (zero on entry)
-  uint32_t* ovf;        // this batch's overflow cursor (zero on entry)
-  uint32_t* povf;       // [tile][bucket] overflow slot of a run that does not fit its sub-region
-  uint64_t* stamps;     // debug: 8 wall-clock stamps per block, or null
-  uint32_t init;        // medium batch: statuses set here (PartLaunch::init)
-  uint64_t* vout;
-  uint32_t* touched;
-  uint32_t delay;       // measurement knob (PMDFC_PART_DELAY_US): each block spins this many 100-MHz ticks at its end
-  // general mixed batches: the joining Gets' resolution (PartLaunch)
-  const uint64_t* iset;
-  uint64_t imask;
-  const uint32_t* icnt;
-  const uint32_t* ipos;
-  uint8_t* early;
-  uint32_t* elink;
-  DevCtl* ctl;
-  uint32_t tag;
-};
 
 // A joining Get of a mixed batch (kStJoin, cceh_kernels.hip k_mixed_get),
 // once k_mixed_join put the batch's inserts of its key into the set (count,
@@ -152,7 +120,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
   __shared__ uint32_t s_cnt[1u << kMaxPartBits];  // ops of the tile per bucket
   __shared__ uint32_t s_reg[1u << kMaxPartBits];  // region slot of the bucket's run
   PART_STAMP(0);
-  const uint32_t nb = 1u << a.p1;
+  const uint32_t nb = 1u << a.pbits;
   for (uint32_t i = threadIdx.x; i < nb; i += kPartThreads) s_cnt[i] = 0;
   __syncthreads();
   const uint64_t base = (uint64_t)blockIdx.x * kPartTile;
@@ -197,7 +165,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
         else if (part) a.st[p] = 2;
       }
       if (part) {
-        const uint32_t b2 = bucket_of(h, a.sbits, a.p1 + a.sbb);  // directory bucket
+        const uint32_t b2 = bucket_of(h, a.sbits, a.pbits + a.sbb);  // directory bucket
         bk[k] = b2 >> a.sbb;
         ro[k] |= (b2 & ((1u << a.sbb) - 1)) << 22;
         if (!(ro[k] & kGetBit)) vv[k] = a.vin[p * a.kvs];
@@ -266,10 +234,6 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
   PART_STAMP(3);
-  if (a.delay && threadIdx.x == 0) {
-    const uint64_t t0 = wall_clock64();
-    while (wall_clock64() - t0 < a.delay) __builtin_amdgcn_s_sleep(2);
-  }
 }
 
 // ------------------------------------------------------------------ helpers
@@ -805,75 +769,6 @@ __device__ __forceinline__ uint32_t wave_split(ulonglong2* __restrict__ pairs, u
 
 // ------------------------------------------------------------------ bucket
 
-struct BucketArgs {
-  const ulonglong2* rkv;
-  const uint32_t* rop;
-  const uint16_t* robk;
-  uint64_t n;            // batch size (op indices are < n)
-  uint32_t chunk;        // ops per wave chunk (<= kCW)
-  uint32_t cap;          // records per bucket region
-  uint32_t capx;         // ... per sub-region (kPartSubs of them)
-  uint64_t ovf_base;
-  const uint32_t* cursor;  // this batch's cursors (kPartSubs per bucket) / overflow count
-  const uint32_t* ovf;
-  uint32_t* cursor_next;   // cleared here for the next batch (clear_next)
-  uint32_t* ovf_next;
-  uint32_t clear_next;     // 0 when the next batch is already being partitioned
-  uint64_t* hdr;
-  uint32_t* pool;
-  uint32_t pool_cap;
-  uint32_t p1, sbb, sbits, shard;
-  uint32_t pfix;         // small sub-directories in fixed slots (cceh_kernels.h kFixedBits)
-  ulonglong2* pairs;
-  uint32_t* occ;
-  uint8_t* ldep;
-  uint64_t* vout;        // mixed only
-  uint8_t* st;
-  uint32_t mixed;
-  uint32_t upsert;       // last-writer-wins Insert
-  const uint16_t* upos;  // upsert: pre-batch key slots (k_upsert_probe)
-  uint32_t max_segments;
-  DevCtl* ctl;
-  uint64_t* wstat;       // per directory bucket: kWStat cumulative counters
-  ulonglong2* wl_kv;     // per directory bucket: kCW parked {key, value}
-  uint32_t* wl_op;       // ... and their rop words
-  uint32_t* wl_n;        // per directory bucket: parked count, or kBigBucket
-  uint64_t* stamps;      // debug: 16 wall-clock stamps per wave, or null
-  uint2* req;            // per directory bucket: kSplitCap split requests
-  uint32_t* reqop;       // ... and the batch position of each request's insert
-  ulonglong2* drops;     // mixed batches with early answers: the drop log (else null)
-  uint32_t* need;
-  uint32_t* gbase;
-  uint32_t* ngrant;
-  uint32_t* newoff;
-  uint64_t* gsh;           // grant shard words, gsplit their requested splits (cceh_kernels.h)
-  uint4* gsplit;
-  uint32_t gcap;
-  uint32_t* act;
-  uint32_t* fbl;         // per bucket: bit 0 k_apply_fast declined it (-> k_apply_fb), bits 1+ declines so far
-  uint32_t* hint;        // host-mapped: the segment count after this batch's grants (k_apply_parked)
-  uint32_t mode;         // k_apply: 0 first pass, 1 parked-op pass, 2 parked-op pass without
-                         // split requests (the last before the final pass)
-  uint32_t* fin;         // k_bucket's worklist of this batch (count: ctl->nfin[par])
-  uint32_t par;
-  // mixed batches: both apply variants are launched and exactly one runs.
-  // gate 1 (MIXED kernels) runs iff ctl->pget == gate_tag (k_mixed_get left
-  // a Get pending), gate 2 (the insert-only kernels) iff not; 0: always
-  uint32_t gate, gate_tag;
-  uint32_t* mseen;       // host-mapped: k_apply<true> stores gate_tag when it runs (BucketLaunch::mseen)
-};
-
-struct ServeArgs {
-  BucketArgs a;                 // the engine at launch (st / vout: 64-entry device scratch)
-  const pmdfc_serve_req* req;   // device mappings of the host rings (wave w: places w * ring_size ...)
-  pmdfc_serve_resp* resp;
-  pmdfc_serve_ctl* ctl;         // one per wave
-  uint64_t ring_size, head0;    // head0: one wave's first place; several waves start at their ctl->head
-  uint32_t nwaves;
-  uint8_t* cbf;                 // counting BF counters, or null
-  uint64_t cbf_m;
-  uint32_t cbf_k;
-};
 constexpr uint32_t kServeHdrMax = 1024;  // directory buckets the serving wave caches in LDS (8 KB)
 constexpr uint64_t kServeWatchdog = 100000000ull;  // wall_clock64 ticks (100 MHz): ~1 s without a heartbeat
 constexpr uint64_t kServeIdle = 100000ull;         // ~1 ms without ops: raise ctl->idle (callers on a CPU-
@@ -3144,36 +3039,8 @@ __global__ __launch_bounds__(64, 1) void k_medium(BucketArgs a, const uint32_t* 
 }
 
 // ---------------------------------------------------------------- split round
-//
-// k_split: one wave per entry of the split list the apply pass granted (a
-// fixed grid looping over ctl->nsplit[par] entries; denied entries are ~0).
-struct SplitArgs {
-  uint32_t par;        // the batch's parity: its grant shards
-  uint32_t pfix;       // small sub-directories grow in their fixed slots
-  uint64_t* stamps;
-  const uint64_t* gsh;
-  const uint4* gsplit;
-  uint32_t gcap;
-  uint32_t* act;       // out: the buckets with requests (k_apply_parked's worklist)
-  uint32_t* gbase;     // out, per bucket: first child id, grants, pool offset, sub-directory bits
-  uint32_t* ngrant;
-  uint32_t* newoff;
-  uint32_t* need;
-  uint32_t max_segments, pool_cap;
-  ulonglong2* pairs;
-  uint32_t* occ;
-  uint8_t* ldep;
-  DevCtl* ctl;
-  const uint32_t* reqop;  // batch position of each request's insert (drop log)
-  ulonglong2* drops;      // the drop log, or null
-  uint32_t team_max;      // split lists up to this long go by teams of four waves
-};
 
 constexpr uint32_t kSplitWaves = 4;      // waves per k_split workgroup
-#ifndef PMDFC_SPLIT_GROUPS
-#define PMDFC_SPLIT_GROUPS 512  // (A/B builds; 1024: two dispatch rounds at 2 waves/SIMD, 12.41-12.44 against 12.56 Gops/s)
-#endif
-constexpr uint32_t kSplitGroups = PMDFC_SPLIT_GROUPS;  // k_split grid (waves loop over the requested splits)
 #ifndef PMDFC_SPLIT_GROUPS_RAMP
 #define PMDFC_SPLIT_GROUPS_RAMP 1024
 #endif
@@ -3247,6 +3114,32 @@ __global__ __launch_bounds__(64 * kSplitWaves, 2) void k_split(SplitArgs a) {
     }
     if (bad) atomicOr(&a.ctl->err, 4u);
   }
+}
+
+// k_split's arguments for the split round of the batch whose passes take `a`
+static SplitArgs split_args(const BucketArgs& a, uint64_t* stamps, uint32_t team_max) {
+  SplitArgs p;
+  p.par = a.par;
+  p.pfix = a.pfix;
+  p.stamps = stamps;
+  p.gsh = a.gsh;
+  p.gsplit = a.gsplit;
+  p.gcap = a.gcap;
+  p.act = a.act;
+  p.gbase = a.gbase;
+  p.ngrant = a.ngrant;
+  p.newoff = a.newoff;
+  p.need = a.need;
+  p.max_segments = a.max_segments;
+  p.pool_cap = a.pool_cap;
+  p.pairs = a.pairs;
+  p.occ = a.occ;
+  p.ldep = a.ldep;
+  p.ctl = a.ctl;
+  p.reqop = a.reqop;
+  p.drops = a.drops;
+  p.team_max = team_max;
+  return p;
 }
 
 // ---------------------------------------------------- lean first apply pass
@@ -3693,23 +3586,6 @@ __global__ __launch_bounds__(64, 2) void k_apply_fb(BucketArgs a) {
   if (threadIdx.x == 0) a.fbl[w] = f + 1u;  // pending bit off, count + 1
 }
 
-// A/B knob: dynamic LDS added to each k_apply_fast wave (lowers its occupancy)
-static uint32_t fast_lds_pad() {
-  static const uint32_t pad = [] {
-    const char* e = getenv("PMDFC_FAST_LDS_PAD");
-    return e ? (uint32_t)atoi(e) : 0u;
-  }();
-  return pad;
-}
-
-bool fast_first_pass() {
-  static const bool on = [] {
-    const char* e = getenv("PMDFC_FAST_APPLY");  // A/B: 0 = the general first pass for every bucket
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // ------------------------------------------------------------- launchers
 
 #ifndef PMDFC_PARKED_GRID
@@ -3735,149 +3611,53 @@ constexpr uint32_t kFinalGridRamp = PMDFC_FINAL_GRID_RAMP;
 
 uint32_t part_blocks(uint64_t n) { return (uint32_t)((n + kPartTile - 1) / kPartTile); }
 
-void launch_part(const PartLaunch& L, hipStream_t s) {
-  if (!L.n) return;
-  PartArgs a;
-  a.keys = L.keys;
-  a.vin = L.vin;
-  a.ops = L.ops;
-  a.st = L.st;
-  a.n = L.n;
-  a.kvs = L.kvs ? L.kvs : 1u;
-  a.sbits = L.sbits;
-  a.shard = L.shard;
-  a.p1 = L.p1 - L.sbb;
-  a.sbb = L.sbb;
-  a.cap = L.cap;
-  a.capx = L.cap / kPartSubs;
-  a.ovf_base = (uint64_t)L.cap << (L.p1 - L.sbb);
-  a.rkv = L.rkv;
-  a.rop = L.rop;
-  a.robk = L.robk;
-  a.cursor = L.cursor;
-  a.ovf = L.ovf;
-  a.stamps = L.stamps;
-  a.init = L.init;
-  a.vout = L.vout;
-  a.touched = L.touched;
-  static const uint32_t delay = [] {
-    const char* e = getenv("PMDFC_PART_DELAY_US");
-    return e ? (uint32_t)(atof(e) * 100.0) : 0u;
-  }();
-  a.delay = delay;
-  a.povf = L.povf;
-  a.iset = L.iset;
-  a.imask = L.imask;
-  a.icnt = L.icnt;
-  a.ipos = L.ipos;
-  a.early = L.early;
-  a.elink = L.elink;
-  a.ctl = L.ctl;
-  a.tag = L.tag;
-  hipLaunchKernelGGL(k_part, dim3(part_blocks(L.n)), dim3(kPartThreads), 0, s, a);
-}
-
-static BucketArgs bucket_args(const BucketLaunch& L) {
-  BucketArgs a;
-  a.rkv = L.rkv;
-  a.rop = L.rop;
-  a.robk = L.robk;
-  a.n = L.n;
-  a.chunk = (L.chunk == 0 || L.chunk > (uint32_t)kCW) ? (uint32_t)kCW : L.chunk;
-  a.cap = L.cap;
-  a.capx = L.cap / kPartSubs;
-  a.ovf_base = (uint64_t)L.cap << (L.p1 - L.sbb);
-  a.cursor = L.cursor;
-  a.ovf = L.ovf;
-  a.cursor_next = L.cursor_next;
-  a.ovf_next = L.ovf_next;
-  a.clear_next = L.clear_next;
-  a.hdr = L.hdr;
-  a.pool = L.pool;
-  a.pool_cap = L.pool_cap;
-  a.p1 = L.p1;
-  a.sbb = L.sbb;
-  a.sbits = L.sbits;
-  a.shard = L.shard;
-  a.pfix = L.pfix;
-  a.pairs = L.pairs;
-  a.occ = L.occ;
-  a.ldep = L.ldep;
-  a.vout = L.vout;
-  a.st = L.st;
-  a.mixed = L.mixed;
-  a.upsert = L.upsert;
-  a.upos = L.upos;
-  a.max_segments = L.max_segments;
-  a.ctl = L.ctl;
-  a.wstat = L.wstat;
-  a.wl_kv = L.wl_kv;
-  a.wl_op = L.wl_op;
-  a.wl_n = L.wl_n;
-  a.stamps = L.stamps;
-  a.req = L.req;
-  a.reqop = L.reqop;
-  a.drops = L.drops;
-  a.need = L.need;
-  a.gbase = L.gbase;
-  a.ngrant = L.ngrant;
-  a.newoff = L.newoff;
-  a.gsh = L.gsh;
-  a.gsplit = L.gsplit;
-  a.gcap = L.gcap;
-  a.act = L.act;
-  a.fbl = L.fbl;
-  a.hint = L.hint;
-  a.mseen = L.mseen;
-  a.mode = 0;
-  a.fin = L.fin;
-  a.par = L.par;
-  a.gate = 0;
-  a.gate_tag = L.gate_tag;
-  return a;
+void launch_part(const PartArgs& a, hipStream_t s) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(k_part, dim3(part_blocks(a.n)), dim3(kPartThreads), 0, s, a);
 }
 
 void launch_apply(const BucketLaunch& L, uint32_t mode, hipStream_t s) {
-  if (!L.n) return;
-  BucketArgs a = bucket_args(L);
+  if (!L.a.n) return;
+  const bool fast = process_knobs().fast_apply;
+  BucketArgs a = L.a;
   a.mode = mode;
-  const dim3 g(1u << L.p1);
+  const dim3 g(1u << a.p1);
   // a gated mixed batch launches the insert-only variant (taken when
   // k_mixed_get answered every Get) and then the mixed one
-  const bool gated = L.mixed && L.gate_tag != 0;
+  const bool gated = a.mixed && a.gate_tag != 0;
   BucketArgs ar = a;
   if (gated) {
     ar.gate = 2;
     a.gate = 1;
   }
   if (mode == 0) {
-    if (gated || !L.mixed) {
-      if (L.upsert && !L.mixed && fast_first_pass()) {
+    if (gated || !a.mixed) {
+      if (a.upsert && !a.mixed && fast) {
         // last-writer-wins, insert-only: the lean pass probes each window
         if (L.wide) hipLaunchKernelGGL(k_apply_fast_ups<true>, g, dim3(64), 0, s, ar);
         else hipLaunchKernelGGL(k_apply_fast_ups<false>, g, dim3(64), 0, s, ar);
-      } else if (!L.upsert && fast_first_pass()) {
+      } else if (!a.upsert && fast) {
         // the lean first pass (launch_apply_fallback: the general one over
         // the buckets it left), its wide variant for large tables
-        if (L.cp) hipLaunchKernelGGL(k_apply_fast_cp, dim3(1u << (L.p1 - kCpSbb)), dim3(64 * kCpWaves), 0, s, ar);
+        if (L.cp) hipLaunchKernelGGL(k_apply_fast_cp, dim3(1u << (a.p1 - kCpSbb)), dim3(64 * kCpWaves), 0, s, ar);
         else if (L.wide) hipLaunchKernelGGL(k_apply_wide, g, dim3(64), 0, s, ar);
-        else hipLaunchKernelGGL(k_apply_fast, g, dim3(64), fast_lds_pad(), s, ar);
+        else hipLaunchKernelGGL(k_apply_fast, g, dim3(64), process_knobs().fast_lds_pad, s, ar);
       } else {
         hipLaunchKernelGGL(k_apply<false>, g, dim3(64), 0, s, ar);
       }
     }
-    if (L.mixed && gated && L.mixed_small)
-      hipLaunchKernelGGL(k_apply_mloop, dim3(std::min(1u << L.p1, kMixedSmallGrid)), dim3(64), 0, s, a);
-    else if (L.mixed)
+    if (a.mixed && gated && L.mixed_small)
+      hipLaunchKernelGGL(k_apply_mloop, dim3(std::min(1u << a.p1, kMixedSmallGrid)), dim3(64), 0, s, a);
+    else if (a.mixed)
       hipLaunchKernelGGL(k_apply<true>, g, dim3(64), 0, s, a);
   } else {
     // worklist passes: a smaller grid (a ramping table's passes carry more work per batch)
-    const dim3 gw(std::min(1u << L.p1, L.ramp ? kParkedGridRamp : kParkedGrid));
+    const dim3 gw(std::min(1u << a.p1, L.ramp ? kParkedGridRamp : kParkedGrid));
     if (gated) {  // (both variants as two launches: configs 3 / 4 7.17-7.25 / 6.04-6.06 against 7.31-7.34 / 6.12-6.15)
       hipLaunchKernelGGL(k_apply_parked_gated, gw, dim3(64), 0, s, ar, a);
     } else {
-      if (gated || !L.mixed) hipLaunchKernelGGL(k_apply_parked<false>, gw, dim3(64), 0, s, ar);
-      if (L.mixed)
+      if (gated || !a.mixed) hipLaunchKernelGGL(k_apply_parked<false>, gw, dim3(64), 0, s, ar);
+      if (a.mixed)
         hipLaunchKernelGGL(k_apply_parked<true>, gated && L.mixed_small ? dim3(std::min(gw.x, kMixedSmallGrid)) : gw,
                            dim3(64), 0, s, a);
     }
@@ -3885,86 +3665,50 @@ void launch_apply(const BucketLaunch& L, uint32_t mode, hipStream_t s) {
 }
 
 void launch_apply_fallback(const BucketLaunch& L, hipStream_t s) {
-  if (!L.n || !fast_first_pass() || (L.upsert && L.mixed)) return;  // (no lean pass was launched)
-  const bool gated = L.mixed && L.gate_tag != 0;
-  if (L.mixed && !gated) return;
-  BucketArgs a = bucket_args(L);
+  if (!L.a.n || !process_knobs().fast_apply || (L.a.upsert && L.a.mixed)) return;  // (no lean pass was launched)
+  const bool gated = L.a.mixed && L.a.gate_tag != 0;
+  if (L.a.mixed && !gated) return;
+  BucketArgs a = L.a;
   if (gated) a.gate = 2;  // with the insert-only variant it follows
-  hipLaunchKernelGGL(k_apply_fb, dim3(1u << L.p1), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_apply_fb, dim3(1u << a.p1), dim3(64), 0, s, a);
 }
 
 void launch_final(const BucketLaunch& L, hipStream_t s) {
-  if (!L.n) return;
-  const dim3 g(std::min(1u << L.p1, L.ramp ? kFinalGridRamp : kFinalGrid));
-  if (L.mixed) hipLaunchKernelGGL(k_bucket<true>, g, dim3(64), 0, s, bucket_args(L));
-  else hipLaunchKernelGGL(k_bucket<false>, g, dim3(64), 0, s, bucket_args(L));
+  if (!L.a.n) return;
+  const dim3 g(std::min(1u << L.a.p1, L.ramp ? kFinalGridRamp : kFinalGrid));
+  if (L.a.mixed) hipLaunchKernelGGL(k_bucket<true>, g, dim3(64), 0, s, L.a);
+  else hipLaunchKernelGGL(k_bucket<false>, g, dim3(64), 0, s, L.a);
 }
 
 void launch_mixed_small(const BucketLaunch& L, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                         hipStream_t s) {
-  if (!L.n) return;
-  BucketArgs a = bucket_args(L);
-  a.stamps = nullptr;
-  if (L.n <= 64) {
+  const BucketArgs& a = L.a;
+  if (!a.n) return;
+  if (a.n <= 64) {
     hipLaunchKernelGGL(k_mixed_tiny, dim3(1), dim3(64), 0, s, a, ops, keys, vin);
     return;
   }
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(L.n, 1ULL << L.p1);  // >= the distinct buckets
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(a.n, 1ULL << a.p1);  // >= the distinct buckets
   hipLaunchKernelGGL(k_mixed_small, dim3(grid), dim3(64), 0, s, a, ops, keys, vin);
 }
 
-void launch_serve(const BucketLaunch& L, const ServeLaunch& V, hipStream_t s) {
-  ServeArgs sa;
-  sa.a = bucket_args(L);
-  sa.a.stamps = nullptr;
-  sa.req = V.req;
-  sa.resp = V.resp;
-  sa.ctl = V.ctl;
-  sa.ring_size = V.ring_size;
-  sa.head0 = V.head0;
-  sa.cbf = V.cbf;
-  sa.cbf_m = V.cbf_m;
-  sa.cbf_k = V.cbf_k;
-  sa.nwaves = V.nwaves ? V.nwaves : 1u;
+void launch_serve(const ServeArgs& sa, hipStream_t s) {
   hipLaunchKernelGGL(k_serve, dim3(sa.nwaves), dim3(64), 0, s, sa);
 }
 
 void launch_medium(const BucketLaunch& L, const uint32_t* touched, hipStream_t s) {
-  if (!L.n) return;
-  const uint32_t npb = 1u << (L.p1 - L.sbb);
-  const dim3 g((uint32_t)std::min<uint64_t>(std::max<uint64_t>(L.n, 64), npb));  // >= the touched buckets
-  if (L.mixed) hipLaunchKernelGGL(k_medium<true>, g, dim3(64), 0, s, bucket_args(L), touched);
-  else hipLaunchKernelGGL(k_medium<false>, g, dim3(64), 0, s, bucket_args(L), touched);
+  const BucketArgs& a = L.a;
+  if (!a.n) return;
+  const uint32_t npb = 1u << (a.p1 - a.sbb);
+  const dim3 g((uint32_t)std::min<uint64_t>(std::max<uint64_t>(a.n, 64), npb));  // >= the touched buckets
+  if (a.mixed) hipLaunchKernelGGL(k_medium<true>, g, dim3(64), 0, s, a, touched);
+  else hipLaunchKernelGGL(k_medium<false>, g, dim3(64), 0, s, a, touched);
 }
 
 void launch_split_round(const BucketLaunch& L, hipStream_t s) {
-  if (!L.n) return;
-  SplitArgs p;
-  p.par = L.par;
-  p.pfix = L.pfix;
-  p.stamps = L.split_stamps;
-  p.gsh = L.gsh;
-  p.gsplit = L.gsplit;
-  p.gcap = L.gcap;
-  p.act = L.act;
-  p.gbase = L.gbase;
-  p.ngrant = L.ngrant;
-  p.newoff = L.newoff;
-  p.need = L.need;
-  p.max_segments = L.max_segments;
-  p.pool_cap = L.pool_cap;
-  p.pairs = L.pairs;
-  p.occ = L.occ;
-  p.ldep = L.ldep;
-  p.ctl = L.ctl;
-  p.reqop = L.reqop;
-  p.drops = L.drops;
-  static const uint32_t team_max = [] {  // PMDFC_SPLIT_TEAM_MAX (A/B): the team-mode cut
-    const char* e = getenv("PMDFC_SPLIT_TEAM_MAX");
-    return e ? (uint32_t)strtoul(e, nullptr, 0) : kSplitGroups;
-  }();
-  p.team_max = team_max;
-  hipLaunchKernelGGL(k_split, dim3(L.ramp ? kSplitGroupsRamp : kSplitGroups), dim3(64 * kSplitWaves), 0, s, p);
+  if (!L.a.n) return;
+  hipLaunchKernelGGL(k_split, dim3(L.ramp ? kSplitGroupsRamp : kSplitGroups), dim3(64 * kSplitWaves), 0, s,
+                     split_args(L.a, L.split_stamps, process_knobs().split_team_max));
 }
 
 }  // namespace pmdfc

@@ -32,6 +32,7 @@
 #include "../../include/pmdfc_cceh.h"
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "knobs.h"
 
 using namespace pmdfc;
 
@@ -159,15 +160,6 @@ struct Timing {
 
 }  // namespace
 
-// partition record buffers (records, cursors, k_part overflow slots): the
-// pipelined insert path keeps up to three batches in flight
-// record buffers: pmdfc_cceh_insert_batches partitions groups of up to
-// kRecBufs / 2 batches ahead (pipe_group); the per-batch pipeline of the
-// routed loop (pipe_batch) reuses a buffer kRecBufs batches later
-#ifndef PMDFC_RECBUFS
-#define PMDFC_RECBUFS 16  // (A/B builds)
-#endif
-constexpr uint32_t kRecBufs = PMDFC_RECBUFS;
 // segments per directory bucket past which the first pass takes its wide
 // variant, and past which k_apply_fb is launched for the buckets it declines
 // (sub-directories past 128 entries)
@@ -197,7 +189,7 @@ struct pmdfc_cceh {
   uint32_t rb = 0;        // record buffer of the next batch (0..kRecBufs-1): records, cursors, k_part overflow
   uint64_t max_segs = 0;
   uint32_t max_batch = 0;
-  uint32_t chunk = 0;     // ops per k_bucket chunk (0 = kernel default)
+  CreateKnobs kn;         // the environment knobs as this engine's create read them (knobs.h)
   uint32_t upsert = 0;    // PMDFC_CFG_UPSERT: last-writer-wins Insert
   uint16_t* upos = nullptr;  // upsert: pre-batch slot of each op's key (max_batch)
 
@@ -213,7 +205,8 @@ struct pmdfc_cceh {
   uint32_t* ipos = nullptr;     // mixed: per set slot, the key's insert position (valid if single)
   uint32_t* islot = nullptr;    // mixed: per op, its insert's set slot (~0: none) -- the verify pass clears it
   uint32_t* icnt = nullptr;     // mixed: per set slot, 1 if the key is inserted more than once
-  uint32_t* icount = nullptr;   // mixed: per 256-op block, the set slots its joining Gets claimed (k_mixed_get -> k_mixed_join -> ctl->ins_total)
+  uint32_t* icount = nullptr;   // mixed: per 256-op block, its inserts (k_mixed_prep / k_mixed_get), summed into the host's
+                                // mode hint and, in insert-set mode, ctl->ins_total (k_mixed_get_iset / k_mixed_join)
   uint32_t* jbits = nullptr;    // mixed: the joining Gets' filter, one per set replica (kJoinWords)
   uint64_t last_mixed_n = 0;    // mixed: the last batch's size (with the pinned insert count: mixed_join_mode)
   uint8_t* early = nullptr;     // mixed: per op, 1 early single-copy hit, 2 linked to its insert
@@ -257,11 +250,11 @@ struct pmdfc_cceh {
   unsigned long long* popc = nullptr;
   uint8_t* srv_st = nullptr;     // serving wave: a chunk's statuses (64) and Get values (64)
   uint64_t* srv_vout = nullptr;
-  uint64_t* stamps = nullptr;  // debug (PMDFC_STAMPS=1): [0, 8*nb) k_bucket, then k_part
-  // (PMDFC_STAMP_ROT=R: R stamp sets, batch i writing set i % R, for a
-  // timeline of consecutive pipelined batches; stamp_cur: this batch's)
+  uint64_t* stamps = nullptr;  // debug (kn.stamps): [0, 8*nb) k_bucket, then k_part
+  // (kn.stamp_rot sets, batch i writing set i % stamp_rot, for a timeline of
+  // consecutive pipelined batches; stamp_cur: this batch's)
   uint64_t* stamp_cur = nullptr;
-  uint32_t stamp_rot = 1, stamp_seq = 0;
+  uint32_t stamp_seq = 0;
 
   // insert_batches: batch i+1 is partitioned on pstream while batch i is
   // applied on the caller's stream
@@ -282,7 +275,6 @@ struct pmdfc_cceh {
   uint32_t* gflat = nullptr;       // flattened directory (pure Gets), 2^kFlatMaxBits entries
   uint32_t* gflat_bits = nullptr;  // its physical depth (device)
   bool flat_valid = false;         // host: no insert since the last flatten
-  uint32_t flat_max = kFlatMaxBits;  // deeper directories skip the flat copy (PMDFC_FLAT_MAX)
 
   Geo geo() const { return Geo{hdr, pool, p1, sbits, shard, nullptr, nullptr}; }
   Geo geo_flat() const { return Geo{hdr, pool, p1, sbits, shard, gflat, gflat_bits}; }
@@ -353,15 +345,6 @@ static void set_geometry(pmdfc_cceh* t, uint32_t p1) {
   t->cp = 0;
 }
 
-// A/B knob: PMDFC_CP=0 keeps the fine partition for every batch
-static bool cp_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("PMDFC_CP");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // The partition geometry of ONE batch, chosen before its launches are filled:
 // insert-only, non-upsert batches of a table at its bucket resolution whose
 // lean pass is the narrow one take the coarse partition (2^(p1 - 3)
@@ -380,8 +363,8 @@ static int batch_geometry(pmdfc_cceh* t, bool insert_only, uint64_t n, hipStream
   // the mean must stay near 2/3 of it (1M ops at p1 = 13: 128)
   const uint64_t tiles = (n + kPartTile - 1) / kPartTile;
   const uint64_t per_sub = t->p1 > kCpSbb ? (((tiles + kPartSubs - 1) / kPartSubs) * kPartTile) >> (t->p1 - kCpSbb) : ~0ull;
-  const bool cp = insert_only && !t->upsert && !t->g_wide && t->p1 == t->p1max && per_sub <= 128 && cp_enabled() &&
-                  fast_first_pass();
+  const bool cp = insert_only && !t->upsert && !t->g_wide && t->p1 == t->p1max && per_sub <= 128 &&
+                  process_knobs().cp && process_knobs().fast_apply;
   const uint32_t sbb = cp ? kCpSbb : (t->p1 > kMaxPartBits ? t->p1 - kMaxPartBits : 0);
   t->cp = cp ? 1u : 0u;
   t->sbb = sbb;
@@ -404,9 +387,10 @@ static int batch_geometry(pmdfc_cceh* t, bool insert_only, uint64_t n, hipStream
 // call's copy left in pinned memory: the host waits for that copy only (one
 // sub-batch back), so the stream keeps a sub-batch queued instead of
 // draining.  Local depths only grow, so a value one sub-batch old is still a
-// lower bound (init_state seeds it with the initial depth after a
-// device-wide sync, so no copy of an earlier table is in flight).  A table
-// at p1max pays nothing.
+// lower bound (init_state seeds it with the initial depth after waiting for
+// the last such copy's event, so no copy of an earlier table lands after the
+// seed; a reset is otherwise stream-ordered, without a device-wide sync).  A
+// table at p1max pays nothing.
 static int rebucket_now(pmdfc_cceh* t, hipStream_t s) {
   if (t->p1 >= t->p1max) return PMDFC_OK;
   if (t->minld_pending) HIPCHK(hipEventSynchronize(t->ev_minld));
@@ -432,15 +416,8 @@ static int rebucket_now(pmdfc_cceh* t, hipStream_t s) {
 // (PMDFC_RAMP_OPS per directory bucket, at least PMDFC_RAMP_MIN: tuning knobs)
 static uint64_t ramp_batch(const pmdfc_cceh* t, uint64_t n) {
   if (t->p1 >= t->p1max) return n;
-  static const uint64_t per = [] {
-    const char* e = getenv("PMDFC_RAMP_OPS");
-    return e && atoi(e) > 0 ? (uint64_t)atoi(e) : 1024ULL;
-  }();
-  static const uint64_t lo = [] {
-    const char* e = getenv("PMDFC_RAMP_MIN");
-    return e && atoi(e) > 0 ? (uint64_t)atoi(e) : 4096ULL;
-  }();
-  return std::min<uint64_t>(n, std::max<uint64_t>(per << t->p1, lo));
+  const ProcessKnobs& K = process_knobs();
+  return std::min<uint64_t>(n, std::max<uint64_t>(K.ramp_ops << t->p1, K.ramp_min));
 }
 
 static int init_state(pmdfc_cceh* t, hipStream_t s) {
@@ -493,65 +470,71 @@ static int init_state(pmdfc_cceh* t, hipStream_t s) {
   return PMDFC_OK;
 }
 
+// The bucket passes' arguments for the batch of record buffer t->rb (B{}: the
+// launchers' a.mode / a.gate, the gated mixed batches' gate_tag / mseen /
+// mixed_small and the drop log stay zero unless the caller sets them).
 static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8_t* st,
                                uint64_t* vout, bool mixed) {
   const uint32_t npb = 1u << (t->p1 - t->sbb);
   const uint32_t p = t->rb;
-  L.n = n;
-  L.rkv = t->rkv + p * t->nrec;
-  L.rop = t->rop + p * t->nrec;
-  L.robk = t->robk + (size_t)p * t->max_batch;
-  L.chunk = t->chunk;
-  L.cap = t->cap;
-  L.cursor = t->cursor + (size_t)p * t->cblk;
-  L.ovf = L.cursor + (size_t)npb * kPartSubs;
-  L.cursor_next = t->cursor + (size_t)((p + 1) % kRecBufs) * t->cblk;
-  L.ovf_next = L.cursor_next + (size_t)npb * kPartSubs;
-  L.clear_next = 1;
-  L.hdr = t->hdr;
-  L.pool = t->pool;
-  L.pool_cap = (uint32_t)t->pool_cap;
-  L.p1 = t->p1;
-  L.sbb = t->sbb;
-  L.sbits = t->sbits;
-  L.shard = t->shard;
-  L.pfix = t->p1 == t->p1max ? 1u : 0u;
-  L.pairs = t->pairs;
-  L.occ = t->occ;
-  L.ldep = t->ldep;
-  L.vout = vout;
-  L.st = st;
-  L.mixed = mixed ? 1u : 0u;
-  L.upsert = t->upsert;
-  L.upos = t->upos;
-  L.max_segments = (uint32_t)t->max_segs;
-  L.ctl = t->ctl;
-  L.wstat = t->wstat;
-  L.wl_kv = t->wl_kv;
-  L.wl_op = t->wl_op;
-  L.wl_n = t->wl_n;
-  L.stamps = t->stamp_cur;
-  L.req = t->req;
-  L.reqop = t->reqop;
-  L.drops = nullptr;  // (mixed batches with early answers set it)
-  L.need = t->need;
-  L.gbase = t->gbase;
-  L.ngrant = t->ngrant;
-  L.newoff = t->newoff;
-  L.gsh = t->gsh;
-  L.gsplit = t->gsplit;
-  L.gcap = t->gcap;
-  L.act = t->act;
-  L.fin = t->fin;
-  L.fbl = t->fbl;
-  L.par = t->parity;
+  BucketArgs& a = L.a;
+  a.n = n;
+  a.rkv = t->rkv + p * t->nrec;
+  a.rop = t->rop + p * t->nrec;
+  a.robk = t->robk + (size_t)p * t->max_batch;
+  a.chunk = (t->kn.chunk == 0 || t->kn.chunk > kChunkWave) ? kChunkWave : t->kn.chunk;
+  a.cap = t->cap;
+  a.capx = t->cap / kPartSubs;
+  a.ovf_base = (uint64_t)t->cap << (t->p1 - t->sbb);
+  a.cursor = t->cursor + (size_t)p * t->cblk;
+  a.ovf = a.cursor + (size_t)npb * kPartSubs;
+  a.cursor_next = t->cursor + (size_t)((p + 1) % kRecBufs) * t->cblk;
+  a.ovf_next = a.cursor_next + (size_t)npb * kPartSubs;
+  a.clear_next = 1;
+  a.hdr = t->hdr;
+  a.pool = t->pool;
+  a.pool_cap = (uint32_t)t->pool_cap;
+  a.p1 = t->p1;
+  a.sbb = t->sbb;
+  a.sbits = t->sbits;
+  a.shard = t->shard;
+  a.pfix = t->p1 == t->p1max ? 1u : 0u;
+  a.pairs = t->pairs;
+  a.occ = t->occ;
+  a.ldep = t->ldep;
+  a.vout = vout;
+  a.st = st;
+  a.mixed = mixed ? 1u : 0u;
+  a.upsert = t->upsert;
+  a.upos = t->upos;
+  a.max_segments = (uint32_t)t->max_segs;
+  a.ctl = t->ctl;
+  a.wstat = t->wstat;
+  a.wl_kv = t->wl_kv;
+  a.wl_op = t->wl_op;
+  a.wl_n = t->wl_n;
+  a.stamps = t->stamp_cur;
+  a.req = t->req;
+  a.reqop = t->reqop;
+  a.drops = nullptr;  // (mixed batches with early answers set it)
+  a.need = t->need;
+  a.gbase = t->gbase;
+  a.ngrant = t->ngrant;
+  a.newoff = t->newoff;
+  a.gsh = t->gsh;
+  a.gsplit = t->gsplit;
+  a.gcap = t->gcap;
+  a.act = t->act;
+  a.fin = t->fin;
+  a.fbl = t->fbl;
+  a.par = t->parity;
   // the lean first pass in its wide variant once the table has more segments
   // per bucket than the narrow one's 32-entry sub-directories hold (about 20:
   // a bucket's deepest segment sits ~1.5 levels below the mean).  The count is
   // a hint the device leaves in pinned memory (k_apply_parked), read without
   // a sync, so it may lag the batches in flight: either variant is exact, and
   // each hands the buckets it cannot take to k_apply_fb.
-  L.hint = t->d_hint;
+  a.hint = t->d_hint;
   L.wide = t->g_wide;  // (batch_geometry)
   L.fb = t->g_fb;
   L.cp = t->cp;
@@ -567,33 +550,44 @@ static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8
   }
 }
 
+// the launches without records (k_mixed_small, k_serve): no phase stamps either
+static void fill_bucket_launch_direct(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8_t* st, uint64_t* vout) {
+  fill_bucket_launch(t, L, n, st, vout, true);
+  L.a.stamps = nullptr;
+}
+
 static uint64_t stamp_words(const pmdfc_cceh* t) {
   return 16ULL * (1ULL << t->p1max) + 8ULL * part_blocks(t->max_batch) + 8ULL * kSplitStamps;
 }
 
-static void fill_part_launch(pmdfc_cceh* t, PartLaunch& L, const uint8_t* ops, const uint64_t* keys,
-                             const uint64_t* vin, uint8_t* st, uint64_t n) {
-  L.keys = keys;
-  L.vin = vin;
-  L.kvs = 1;
-  L.ops = ops;
-  L.st = st;
-  L.n = n;
-  L.sbits = t->sbits;
-  L.shard = t->shard;
-  L.p1 = t->p1;
-  L.sbb = t->sbb;
-  L.cap = t->cap;
-  const uint32_t p = t->rb, npb = 1u << (t->p1 - t->sbb);
-  L.rkv = t->rkv + p * t->nrec;
-  L.rop = t->rop + p * t->nrec;
-  L.robk = t->robk + (size_t)p * t->max_batch;
-  L.cursor = t->cursor + (size_t)p * t->cblk;
-  L.ovf = L.cursor + (size_t)npb * kPartSubs;
-  L.povf = t->povf + (size_t)p * part_blocks(t->max_batch) * (1u << kMaxPartBits);
+// k_part's arguments for the batch of record buffer t->rb (P{}: the medium
+// batches' init / vout / touched and the mixed batches' join group stay zero
+// unless the caller sets them); kvs: 1 for key / value arrays, 2 for records
+static void fill_part_launch(pmdfc_cceh* t, PartArgs& a, const uint8_t* ops, const uint64_t* keys,
+                             const uint64_t* vin, uint32_t kvs, uint8_t* st, uint64_t n) {
+  a.keys = keys;
+  a.vin = vin;
+  a.kvs = kvs ? kvs : 1u;
+  a.ops = ops;
+  a.st = st;
+  a.n = n;
+  a.sbits = t->sbits;
+  a.shard = t->shard;
+  a.pbits = t->p1 - t->sbb;
+  a.sbb = t->sbb;
+  a.cap = t->cap;
+  a.capx = t->cap / kPartSubs;
+  a.ovf_base = (uint64_t)t->cap << a.pbits;
+  const uint32_t p = t->rb, npb = 1u << a.pbits;
+  a.rkv = t->rkv + p * t->nrec;
+  a.rop = t->rop + p * t->nrec;
+  a.robk = t->robk + (size_t)p * t->max_batch;
+  a.cursor = t->cursor + (size_t)p * t->cblk;
+  a.ovf = a.cursor + (size_t)npb * kPartSubs;
+  a.povf = t->povf + (size_t)p * part_blocks(t->max_batch) * (1u << kMaxPartBits);
   // (each batch's partition comes first: it takes the batch's stamp set)
-  t->stamp_cur = t->stamps ? t->stamps + (uint64_t)(t->stamp_seq++ % t->stamp_rot) * stamp_words(t) : nullptr;
-  L.stamps = t->stamp_cur ? t->stamp_cur + (16ULL << t->p1max) : nullptr;
+  t->stamp_cur = t->stamps ? t->stamps + (uint64_t)(t->stamp_seq++ % t->kn.stamp_rot) * stamp_words(t) : nullptr;
+  a.stamps = t->stamp_cur ? t->stamp_cur + (16ULL << t->p1max) : nullptr;
 }
 
 // The bucket passes of one insert / mixed batch, all on the stream: a first
@@ -671,17 +665,15 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   // (floor: a routed engine's max_batch is 2^shard_bits padded owner blocks,
   // ~1.07x the ops it actually receives per batch)
   const uint32_t lgb = cfg->max_batch ? 31u - (uint32_t)__builtin_clz(cfg->max_batch) : 0u;
-  uint32_t p1t = lgb > 7 ? lgb - 7 : 0;
-  if (const char* e = getenv("PMDFC_P1MAX")) p1t = (uint32_t)atoi(e);  // A/B (capped at kMaxP1 below)
+  const uint32_t p1t = lgb > 7 ? lgb - 7 : 0;
   // never finer than the initial directory at first (a segment must not
   // span two buckets); rebucket_now refines up to p1max as segments deepen
-  t->p1max = std::min<uint32_t>(p1t, kMaxP1);
+  t->kn = CreateKnobs::read();
+  t->p1max = t->kn.p1max >= 0 ? (uint32_t)t->kn.p1max : std::min<uint32_t>(p1t, kMaxP1);
   t->p1_init = std::min<uint32_t>(t->p1max, Dl0);
   // k_part partitions into at most 2^kMaxPartBits buckets; finer directory
   // buckets share a partition bucket (sub-buckets)
   set_geometry(t, t->p1_init);
-  if (const char* e = getenv("PMDFC_CHUNK")) t->chunk = (uint32_t)atoi(e);
-  if (const char* e = getenv("PMDFC_FLAT_MAX")) t->flat_max = std::min<uint32_t>((uint32_t)atoi(e), kFlatMaxBits);
   uint64_t ms = cfg->max_segments;
   if (ms == 0) {
     size_t fr = 0, tot = 0;
@@ -723,9 +715,9 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   ALLOC(t->occ, ms * 32 * sizeof(uint32_t));
   ALLOC(t->ldep, ms);
   {
-    // the mixed batches' key set: kJoinReps replicas (k_mixed_get), each at
-    // load <= 1/2 for its blocks' joining keys (>= 8192 slots: a replica takes
-    // whole 256-op blocks, so a small batch may put one block in one replica)
+    // the mixed batches' key set: ONE table at load <= 1/2 even when every op
+    // of a batch inserts a distinct key (at least 8192 slots).  Only the
+    // joining Gets' filter (jbits) is replicated, kJoinReps times.
     uint64_t isl = 8192;
     while (isl < 2 * (uint64_t)t->max_batch) isl <<= 1;
     t->imask = isl - 1;
@@ -777,21 +769,17 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   ALLOC(t->popc, sizeof(unsigned long long));
   ALLOC(t->srv_st, 64);
   ALLOC(t->srv_vout, 64 * sizeof(uint64_t));
-  if (const char* ev = getenv("PMDFC_STAMPS"))
-    if (ev[0] == '1') {
-      const char* r = getenv("PMDFC_STAMP_ROT");
-      t->stamp_rot = r && atoi(r) > 1 ? (uint32_t)atoi(r) : 1u;
-      ALLOC(t->stamps, t->stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t));
-      HIPCHK(hipMemset(t->stamps, 0, t->stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t)));
-      t->stamp_cur = t->stamps;
-    }
+  if (t->kn.stamps) {
+    ALLOC(t->stamps, t->kn.stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t));
+    HIPCHK(hipMemset(t->stamps, 0, t->kn.stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t)));
+    t->stamp_cur = t->stamps;
+  }
 #undef ALLOC
   {
     // the partition stream at high priority: a batch's k_part is dispatched
     // ahead of the previous batch's remaining bucket waves (PMDFC_PSTREAM_PRIO=0: default priority, A/B)
     int lo = 0, hi = 0;
-    const char* pe = getenv("PMDFC_PSTREAM_PRIO");
-    if (!(pe && pe[0] == '0') && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
+    if (t->kn.pstream_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
       e = hipStreamCreateWithPriority(&t->pstream, hipStreamNonBlocking, hi);
     else
       e = hipStreamCreateWithFlags(&t->pstream, hipStreamNonBlocking);
@@ -875,7 +863,7 @@ static int do_get(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* vout, uint8_t
   hipStream_t s = (hipStream_t)stream;
   const bool count = t->count_lines && n <= t->max_batch;
   if (!t->flat_valid) {  // first Get after inserts: flatten the directory
-    launch_flatten(t->hdr, t->pool, t->p1, t->gflat, t->gflat_bits, t->flat_max, s);
+    launch_flatten(t->hdr, t->pool, t->p1, t->gflat, t->gflat_bits, t->kn.flat_max, s);
     t->flat_valid = true;
   }
   t->timing.begin(PMDFC_K_GET, s);
@@ -884,9 +872,7 @@ static int do_get(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* vout, uint8_t
   t->last_get_n = n;
   t->last_get_counted = count;
   {
-    const char* e = getenv("PMDFC_GET_UNROLL");
-    int U = e ? atoi(e) : 2;
-    if (U != 1 && U != 2 && U != 4) U = 2;
+    const int U = process_knobs().get_unroll;  // (as launch_get)
     t->last_get_blocks = ((n + U - 1) / U + 63) / 64;
   }
   HIPCHK(hipGetLastError());
@@ -938,13 +924,7 @@ int pmdfc_cceh_get_records(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* resp
 // A batch of at most kChunkWave ops takes one launch (k_mixed_small) instead
 // of the ~12 of the general pipeline; its results are the serial reference's
 // exactly.  PMDFC_SMALL_MAX lowers the cut (0: never; A/B and tests).
-static uint64_t small_max() {
-  static const uint64_t v = [] {
-    const char* e = getenv("PMDFC_SMALL_MAX");
-    return e ? std::min<uint64_t>(strtoull(e, nullptr, 0), kChunkWave) : (uint64_t)kChunkWave;
-  }();
-  return v;
-}
+static uint64_t small_max() { return process_knobs().small_max; }
 
 static int small_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                      uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
@@ -952,7 +932,7 @@ static int small_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   if (rc) return rc;
   if ((rc = batch_geometry(t, false, n, s, false))) return rc;  // (no records)
   BucketLaunch B{};
-  fill_bucket_launch(t, B, n, st, vout, true);
+  fill_bucket_launch_direct(t, B, n, st, vout);
   t->timing.begin(PMDFC_K_PROCESS, s);
   launch_mixed_small(B, ops, keys, vin, s);
   t->timing.end(s);
@@ -967,21 +947,14 @@ static int small_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
 // touched buckets listed) and k_medium, the final pass over every touched
 // bucket with its records in batch order.  Exact serial results (no early
 // answers).  PMDFC_MEDIUM_MAX lowers the cut (0: never).
-static uint64_t medium_max() {
-  static const uint64_t v = [] {
-    const char* e = getenv("PMDFC_MEDIUM_MAX");
-    return e ? std::min<uint64_t>(strtoull(e, nullptr, 0), kPartTile) : (uint64_t)kPartTile;
-  }();
-  return v;
-}
+static uint64_t medium_max() { return process_knobs().medium_max; }
 
 static int medium_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin, uint32_t kvs,
                       uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
   int rc = batch_geometry(t, false, n, s);
   if (rc) return rc;
-  PartLaunch P{};
-  fill_part_launch(t, P, ops, keys, vin, st, n);
-  P.kvs = kvs;
+  PartArgs P{};
+  fill_part_launch(t, P, ops, keys, vin, kvs, st, n);
   P.init = ops ? 1u : 0u;
   P.vout = vout;
   P.touched = t->touched;
@@ -1007,17 +980,16 @@ static int insert_one(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
                       uint64_t n, hipStream_t s) {
   int rc = batch_geometry(t, true, n, s);
   if (rc) return rc;
-  PartLaunch P{};
-  fill_part_launch(t, P, nullptr, keys, vin, st, n);
-  P.kvs = kvs;
+  PartArgs P{};
+  fill_part_launch(t, P, nullptr, keys, vin, kvs, st, n);
   BucketLaunch B{};
   fill_bucket_launch(t, B, n, st, nullptr, false);
   t->timing.begin(PMDFC_K_ROUTE, s);
   // upsert: the lean first pass probes each window itself; the pre-batch
   // probe serves the general pass only when the lean one is off
-  const bool probe = t->upsert && !fast_first_pass();
+  const bool probe = t->upsert && !process_knobs().fast_apply;
   if (probe) launch_upsert_probe(keys, kvs, nullptr, n, t->geo(), t->pairs, t->upos, s);
-  else B.upos = nullptr;
+  else B.a.upos = nullptr;
   launch_part(P, s);
   run_bucket_passes(t, B, s);
   t->timing.end(s);
@@ -1096,11 +1068,10 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   HIPCHK(hipMemsetAsync(t->cursor + p * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
   int rc = batch_geometry(t, true, n, nullptr, false);  // (its cursors: zeroed just above)
   if (rc) return rc;
-  PartLaunch PL{};
-  fill_part_launch(t, PL, nullptr, keys, vin, st, n);
-  PL.kvs = kvs;
+  PartArgs PL{};
+  fill_part_launch(t, PL, nullptr, keys, vin, kvs, st, n);
   hipEvent_t e0 = t->timing.span_begin(P);
-  const bool probe = t->upsert && !fast_first_pass();  // (as insert_one)
+  const bool probe = t->upsert && !process_knobs().fast_apply;  // (as insert_one)
   if (probe) {  // the probe reads the table: after the previous batch (ev_done)
     if (k >= 1) HIPCHK(hipStreamWaitEvent(P, t->ev_done[(p + kRecBufs - 1) % kRecBufs], 0));
     launch_upsert_probe(keys, kvs, nullptr, n, t->geo(), t->pairs, t->upos, P);
@@ -1111,8 +1082,8 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   HIPCHK(hipStreamWaitEvent(s, t->ev_part[p], 0));
   BucketLaunch B{};
   fill_bucket_launch(t, B, n, st, nullptr, false);
-  B.clear_next = 0;  // the next batch's cursors may already be in use
-  if (!probe) B.upos = nullptr;
+  B.a.clear_next = 0;  // the next batch's cursors may already be in use
+  if (!probe) B.a.upos = nullptr;
   run_bucket_passes(t, B, s);
   t->timing.end(s);
   HIPCHK(hipEventRecord(t->ev_done[p], s));
@@ -1130,15 +1101,7 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
 // batches.  Group g's records reuse group g - 2's buffers (kRecBufs = 2 G_max),
 // so its partitions wait for that group's passes only; they run under group
 // g - 1's passes.  Each batch keeps the geometry its partition chose.
-static uint32_t pipe_group_size() {
-  static const uint32_t g = [] {
-    const char* e = getenv("PMDFC_PIPE_GROUP");  // A/B: 1 = an event pair per batch
-    const int v = e ? atoi(e) : 8;
-    return (uint32_t)std::min<int>(std::max<int>(v, 1), (int)kRecBufs / 2);
-  }();
-  return g;
-}
-
+// (PMDFC_PIPE_GROUP: G; 1 = an event pair per batch)
 static int pipe_group(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin, uint8_t* st,
                       const uint64_t* bounds, const uint32_t* idx, uint32_t m, hipStream_t s, uint32_t gi) {
   hipStream_t P = t->pstream;
@@ -1153,8 +1116,8 @@ static int pipe_group(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
     const uint32_t p = t->rb;
     HIPCHK(hipMemsetAsync(t->cursor + p * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
     if (int rc = batch_geometry(t, true, n, nullptr, false)) return rc;  // (its cursors: zeroed just above)
-    PartLaunch PL{};
-    fill_part_launch(t, PL, nullptr, keys + o, vin + o, st + o, n);
+    PartArgs PL{};
+    fill_part_launch(t, PL, nullptr, keys + o, vin + o, 1, st + o, n);
     launch_part(PL, P);
     geo[j] = {p, t->sbb, t->cap, t->cp, t->g_wide, t->g_fb, t->stamp_cur};
     t->rb = (p + 1) % kRecBufs;
@@ -1174,8 +1137,8 @@ static int pipe_group(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
     t->stamp_cur = geo[j].stamps;
     BucketLaunch B{};
     fill_bucket_launch(t, B, n, st + o, nullptr, false);
-    B.clear_next = 0;  // the next batch's cursors may already be in use
-    B.upos = nullptr;
+    B.a.clear_next = 0;  // the next batch's cursors may already be in use
+    B.a.upos = nullptr;
     run_bucket_passes(t, B, s);
     t->timing.end(s);
     t->batches += 1;
@@ -1216,7 +1179,7 @@ int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint6
   // the partition stream starts after everything already on the caller's
   // stream (the inputs, and every earlier batch)
   int rc = pipe_begin(t, s);
-  if (t->upsert && !fast_first_pass()) {  // (the upsert probe reads the table: batch by batch)
+  if (t->upsert && !process_knobs().fast_apply) {  // (the upsert probe reads the table: batch by batch)
     uint32_t k = 0;
     for (uint32_t i = i0; i < nbatches && rc == PMDFC_OK; ++i) {
       const uint64_t o = bounds[i], n = bounds[i + 1] - bounds[i];
@@ -1225,7 +1188,7 @@ int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint6
     }
     return rc ? rc : pipe_end(t, s);
   }
-  const uint32_t G = pipe_group_size();
+  const uint32_t G = process_knobs().pipe_group;
   uint32_t idx[kRecBufs / 2 > 0 ? kRecBufs / 2 : 1], m = 0, gi = 0;
   for (uint32_t i = i0; i <= nbatches && rc == PMDFC_OK; ++i) {
     if (i < nbatches && bounds[i + 1] > bounds[i]) idx[m++] = i;
@@ -1237,15 +1200,6 @@ int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint6
   return rc ? rc : pipe_end(t, s);
 }
 
-// PMDFC_MIXED_SMALL=0: the mixed passes of gated batches always on full grids (A/B)
-static bool mixed_small_off() {
-  static const bool v = [] {
-    const char* e = getenv("PMDFC_MIXED_SMALL");
-    return e && e[0] == '0';
-  }();
-  return v;
-}
-
 // A mixed batch tells its Gets whether the batch inserts their key through
 // the JOIN (the Gets that need it claim their keys, the inserts look them up)
 // when the last mixed batch inserted more than 1/8 of its ops, else through
@@ -1255,10 +1209,7 @@ static bool mixed_small_off() {
 // leaves in pinned memory, read without a sync: either mode is exact.
 // PMDFC_MIXED_JOIN=0 / 1 forces one (A/B, tests).
 static bool mixed_join_mode(pmdfc_cceh* t, uint64_t n) {
-  static const int force = [] {
-    const char* e = getenv("PMDFC_MIXED_JOIN");
-    return e ? atoi(e) : -1;
-  }();
+  const int force = process_knobs().mixed_join;
   if (force >= 0) return force != 0;
   (void)n;
   const uint64_t last = __atomic_load_n(t->h_hint + kHintMixIns, __ATOMIC_RELAXED);
@@ -1298,8 +1249,8 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
                           t->elink, t->ctl, tag, t->icount, t->upsert ? 1u : 0u, hint_ins, s);
   }
   t->last_mixed_n = n;
-  PartLaunch P{};
-  fill_part_launch(t, P, ops, keys, vin, st, n);
+  PartArgs P{};
+  fill_part_launch(t, P, ops, keys, vin, 1, st, n);
   P.iset = t->iset;
   P.imask = t->imask;
   P.icnt = t->icnt;
@@ -1313,15 +1264,16 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   fill_bucket_launch(t, B, n, st, vout, true);
   // when k_mixed_get answered every Get, the insert-only apply passes run
   // (upsert batches always take the mixed ones)
-  B.gate_tag = t->upsert ? 0u : tag;
+  B.a.gate_tag = t->upsert ? 0u : tag;
   // the mixed passes on small grids unless a mixed batch of the last 64 ran
   // them (the word may lag the batches in flight: either grid is exact)
-  B.mseen = t->d_hint + kHintMixed;
+  B.a.mseen = t->d_hint + kHintMixed;
   {
     const uint32_t last = __atomic_load_n(t->h_hint + kHintMixed, __ATOMIC_RELAXED);
-    B.mixed_small = (last != 0 && tag - last < 64u) || mixed_small_off() ? 0u : 1u;
+    // (PMDFC_MIXED_SMALL=0: always on full grids)
+    B.mixed_small = (last != 0 && tag - last < 64u) || !process_knobs().mixed_small ? 0u : 1u;
   }
-  B.drops = t->drops;  // splits log what they drop, for k_mixed_verify
+  B.a.drops = t->drops;  // splits log what they drop, for k_mixed_verify
   t->timing.begin(PMDFC_K_ROUTE, s);
   if (t->upsert) launch_upsert_probe(keys, 1, ops, n, t->geo(), t->pairs, t->upos, s);
   launch_part(P, s);
@@ -1421,8 +1373,9 @@ static int serve_start(pmdfc_cceh_t* t, uint32_t nwaves, pmdfc_serve_req* req, p
   HIPCHK(hipHostGetDevicePointer(&dc, ctl, 0));
   if ((rc = batch_geometry(t, false, 64, s, false))) return rc;  // (no records)
   BucketLaunch B{};
-  fill_bucket_launch(t, B, 64, t->srv_st, t->srv_vout, true);
-  ServeLaunch V{};
+  fill_bucket_launch_direct(t, B, 64, t->srv_st, t->srv_vout);
+  ServeArgs V{};
+  V.a = B.a;
   V.req = (const pmdfc_serve_req*)dq;
   V.resp = (pmdfc_serve_resp*)dr;
   V.ctl = (pmdfc_serve_ctl*)dc;
@@ -1431,8 +1384,8 @@ static int serve_start(pmdfc_cceh_t* t, uint32_t nwaves, pmdfc_serve_req* req, p
   V.cbf = cbf ? cbf->cnt : nullptr;
   V.cbf_m = cbf ? cbf->nbits : 0;
   V.cbf_k = cbf ? cbf->k : 0;
-  V.nwaves = nwaves;
-  launch_serve(B, V, s);
+  V.nwaves = nwaves ? nwaves : 1u;
+  launch_serve(V, s);
   HIPCHK(hipGetLastError());
   t->flat_valid = false;
   return PMDFC_OK;
@@ -1624,8 +1577,8 @@ int pmdfc_cceh_debug_stamps(pmdfc_cceh_t* t, uint64_t* out, uint64_t n, uint32_t
   DevGuard g(t->dev);
   HIPCHK(hipDeviceSynchronize());
   // the last batch's set, or every set when n holds them all (PMDFC_STAMP_ROT)
-  const uint64_t tot = stamp_words(t), all = tot * t->stamp_rot;
-  const bool every = t->stamp_rot > 1 && n >= all;
+  const uint64_t tot = stamp_words(t), all = tot * t->kn.stamp_rot;
+  const bool every = t->kn.stamp_rot > 1 && n >= all;
   const uint64_t* src = every ? t->stamps : (t->stamp_cur ? t->stamp_cur : t->stamps);
   HIPCHK(hipMemcpy(out, src, std::min(n, every ? all : tot) * 8, hipMemcpyDeviceToHost));
   if (nbuckets) *nbuckets = 1u << t->p1max;  // (the stamp rows are laid out for p1max)
@@ -2454,11 +2407,7 @@ static int route_batches(pmdfc_router_t* r, pmdfc_cceh_t* t, pmdfc_comm_t* c, ui
   hipStream_t S = (hipStream_t)stream, C = c->cs;
   // PMDFC_ROUTE_DIRECT=0: the pack / exchange / unpack path even on one rank
   // (its per-batch cost, measured where no peer exists; A/B and tests)
-  static const bool direct_ok = [] {
-    const char* e = getenv("PMDFC_ROUTE_DIRECT");
-    return !(e && e[0] == '0');
-  }();
-  if (direct_ok && c->nranks == 1 && r->cfg.cap >= r->cfg.max_batch) {
+  if (process_knobs().route_direct && c->nranks == 1 && r->cfg.cap >= r->cfg.max_batch) {
     // One rank: every op's owner is this rank, its block never moves and
     // holds a whole batch (cap >= max_batch: no carry can form), so the
     // routed call IS the direct call in batch order -- the engine runs on
@@ -2583,10 +2532,7 @@ static int route_batches(pmdfc_router_t* r, pmdfc_cceh_t* t, pmdfc_comm_t* c, ui
   // batch first
   // (PMDFC_ROUTE_PIPE=1; measured slower on one rank: the partitions ran at
   // ~100 us beside the packs instead of ~40 us inline)
-  static const bool pipe_inserts = [] {
-    const char* e = getenv("PMDFC_ROUTE_PIPE");
-    return e && atoi(e) != 0;
-  }();
+  const bool pipe_inserts = process_knobs().route_pipe;
   uint32_t piped = 0;
   auto run = [&](uint64_t i) -> int {
     int e = PMDFC_OK;

@@ -107,23 +107,58 @@ constexpr uint32_t kMaxPartBits = 13;      // <= 8192 partition buckets
 // it whole, and each region cursor is bumped by 1/8 of the blocks.
 constexpr uint32_t kPartSubs = 8;
 uint32_t part_blocks(uint64_t n);
-struct PartLaunch {
+constexpr uint32_t kSplitStamps = 8192;
+// Split requests are granted through kGShards pairs of counters, one per XCD
+// (bucket w -> shard w % 8, the XCD its first-pass wave runs on), each word
+// on a 128-B line of its own: {child segments [0,32) | requesting buckets
+// [32,64)} and the sub-directory pool entries requested in this batch.  A
+// contended single word serializes at ~88 atomics/us, far below the rate of
+// a split-heavy batch's ~8k requests.
+constexpr uint32_t kGShards = 8;
+constexpr uint32_t kGStride = 32;  // u64 words per shard: the segment word at 0, the pool word at 16
+constexpr uint32_t kChunkWave = 256;  // ops per k_apply / k_bucket wave chunk (mean load: 128)
+constexpr uint32_t kSplitCap = 64;    // split requests per directory bucket and round
+// per-bucket cumulative counters: lines, waited, splits, split loss, runs,
+// rounds, {max rounds | max local depth << 16 | growths << 32}, spare
+constexpr int kWStat = 8;
+#ifndef PMDFC_SPLIT_GROUPS
+#define PMDFC_SPLIT_GROUPS 512  // (A/B builds; 1024: two dispatch rounds at 2 waves/SIMD, 12.41-12.44 against 12.56 Gops/s)
+#endif
+constexpr uint32_t kSplitGroups = PMDFC_SPLIT_GROUPS;  // k_split grid (waves loop over the requested splits)
+// partition record buffers (records, cursors, k_part overflow slots):
+// pmdfc_cceh_insert_batches partitions groups of up to kRecBufs / 2 batches
+// ahead (pipe_group); the per-batch pipeline of the routed loop (pipe_batch)
+// reuses a buffer kRecBufs batches later
+#ifndef PMDFC_RECBUFS
+#define PMDFC_RECBUFS 16  // (A/B builds)
+#endif
+constexpr uint32_t kRecBufs = PMDFC_RECBUFS;
+
+// The argument structs of bucket.hip's kernels, passed by value.  The engine
+// fills them (cceh_engine.hip fill_part_launch / fill_bucket_launch and the
+// callers that patch a batch kind's fields); the launchers add only what
+// they decide: the kernel, the grid and the gate values.
+
+// k_part
+struct PartArgs {
   const uint64_t* keys;
   const uint64_t* vin;
-  const uint8_t* ops;  // null: insert-only
+  const uint8_t* ops;   // null: insert-only batch (k_part resolves statuses itself)
   uint8_t* st;
   uint64_t n;
-  uint32_t kvs;        // key/value stride in u64 words (0/1: arrays; 2: {key, value} records)
+  uint32_t kvs;         // u64 words from one op's key (value) to the next: 1 (arrays), or 2 for {key, value} records
   uint32_t sbits, shard;
-  uint32_t p1, sbb;    // directory bucket bits, of which sbb sub-bucket bits
-  uint32_t cap;        // record slots per partition bucket
-  ulonglong2* rkv;
-  uint32_t* rop;
-  uint16_t* robk;
-  uint32_t* cursor;    // this batch's parity
-  uint32_t* ovf;
-  uint32_t* povf;      // [tile][partition bucket] overflow slots (this batch's parity)
-  uint64_t* stamps;    // debug phase stamps or null
+  uint32_t pbits, sbb;  // partition bucket bits (directory bucket bits - sbb); sbb: sub-bucket bits
+  uint32_t cap;         // record slots per partition bucket region
+  uint32_t capx;        // ... per sub-region (cap / kPartSubs)
+  uint64_t ovf_base;    // first overflow record slot
+  ulonglong2* rkv;      // records: {key, value}
+  uint32_t* rop;        // records: op index | sub-bucket << 22 | Get << 31
+  uint16_t* robk;       // partition bucket of each overflow record
+  uint32_t* cursor;     // this batch's cursors, [sub-region][partition bucket] (zero on entry)
+  uint32_t* ovf;        // this batch's overflow cursor (zero on entry)
+  uint32_t* povf;       // [tile][partition bucket] overflow slot of a run that does not fit its sub-region
+  uint64_t* stamps;     // debug: 8 wall-clock stamps per block, or null
   // a medium mixed batch (one partition block, k_medium after): statuses
   // initialized here (k_mixed_prep's rule), Get values zeroed, and the
   // partition buckets that received ops listed ([0] count, then the buckets)
@@ -141,89 +176,88 @@ struct PartLaunch {
   DevCtl* ctl;
   uint32_t tag;
 };
-void launch_part(const PartLaunch& L, hipStream_t s);
-struct BucketLaunch {
-  uint64_t n;
+void launch_part(const PartArgs& a, hipStream_t s);
+
+// the apply passes, k_bucket, k_medium, k_mixed_small / k_mixed_tiny, k_serve
+struct BucketArgs {
   const ulonglong2* rkv;
   const uint32_t* rop;
   const uint16_t* robk;
-  uint32_t chunk;
-  uint32_t cap;       // records per partition bucket region (kPartSubs sub-regions of cap / kPartSubs)
-  const uint32_t* cursor;  // [kPartSubs][partition buckets] cursors, then the overflow cursor
+  uint64_t n;            // batch size (op indices are < n)
+  uint32_t chunk;        // ops per wave chunk (<= kChunkWave)
+  uint32_t cap;          // records per partition bucket region
+  uint32_t capx;         // ... per sub-region (kPartSubs of them)
+  uint64_t ovf_base;
+  const uint32_t* cursor;  // this batch's [kPartSubs][partition buckets] cursors, then the overflow cursor
   const uint32_t* ovf;
-  uint32_t* cursor_next;
+  uint32_t* cursor_next;   // cleared here for the next batch (clear_next)
   uint32_t* ovf_next;
-  uint32_t clear_next;  // first apply pass zeroes the other parity's cursors (one batch per call)
+  uint32_t clear_next;     // the first apply pass zeroes the other parity's cursors (one batch per call);
+                           // 0 when the next batch is already being partitioned
   uint64_t* hdr;
   uint32_t* pool;
   uint32_t pool_cap;
-  uint32_t p1, sbb, sbits, shard;
-  uint32_t pfix;      // p1 == p1max: small sub-directories live (and grow) in their fixed slots
+  uint32_t p1, sbb, sbits, shard;  // p1: directory bucket bits
+  uint32_t pfix;         // p1 == p1max: small sub-directories live (and grow) in their fixed slots (kFixedBits)
   ulonglong2* pairs;
   uint32_t* occ;
   uint8_t* ldep;
-  uint64_t* vout;
+  uint64_t* vout;        // mixed only
   uint8_t* st;
   uint32_t mixed;
-  uint32_t upsert;    // last-writer-wins Insert (PMDFC_CFG_UPSERT)
+  uint32_t upsert;       // last-writer-wins Insert (PMDFC_CFG_UPSERT)
   const uint16_t* upos;  // upsert: pre-batch slot of each op's key (k_upsert_probe), first pass only
   uint32_t max_segments;
   DevCtl* ctl;
-  uint64_t* wstat;    // per directory bucket stat slots (kWStat each)
-  ulonglong2* wl_kv;  // parked ops: kChunkWave per directory bucket
-  uint32_t* wl_op;
-  uint32_t* wl_n;
-  uint64_t* stamps;  // debug phase stamps or null
+  uint64_t* wstat;       // per directory bucket: kWStat cumulative counters
+  ulonglong2* wl_kv;     // per directory bucket: kChunkWave parked {key, value}
+  uint32_t* wl_op;       // ... and their rop words
+  uint32_t* wl_n;        // per directory bucket: parked count, or kBigBucket
+  uint64_t* stamps;      // debug: 16 wall-clock stamps per wave, or null
   // pipelined split rounds (an apply pass requests and grants -> k_split)
-  uint2* req;        // kSplitCap split requests per directory bucket
-  uint32_t* reqop;   // ... the batch position of each request's insert
-  ulonglong2* drops; // mixed batches with early answers: the drop log (cceh_device.h kDropLog), else null
-  uint32_t* need;    // per bucket: sub-directory bits those requests need (0: none)
-  uint32_t* gbase;   // per bucket: first child segment id granted
-  uint32_t* ngrant;  // per bucket: requests granted, committed by the owner's next pass
-  uint32_t* newoff;  // per bucket: pool offset of the grown sub-directory
-  uint64_t* gsh;     // [2][kGShards] grant shard words by batch parity (kGStride apart)
-  uint4* gsplit;     // [2][kGShards][gcap] the requested splits by segment offset in their shard:
-                     // {request word, w | i << 14 | entry << 20, pool offset, nr | need << 8}
-  uint32_t gcap;     // splits per shard (kSplitCap x the shard's buckets)
-  uint32_t* act;     // [2^p1] buckets with requests (k_split -> k_apply_parked)
-  uint32_t* fbl;     // [2^p1max] per bucket: declined by k_apply_fast (bit 0), decline count (bits 1+)
-  uint64_t* split_stamps;  // debug: 8 stamps for each of the first kSplitStamps splits, or null
+  uint2* req;            // kSplitCap split requests per directory bucket
+  uint32_t* reqop;       // ... the batch position of each request's insert
+  ulonglong2* drops;     // mixed batches with early answers: the drop log (cceh_device.h kDropLog), else null
+  uint32_t* need;        // per bucket: sub-directory bits those requests need (0: none)
+  uint32_t* gbase;       // per bucket: first child segment id granted
+  uint32_t* ngrant;      // per bucket: requests granted, committed by the owner's next pass
+  uint32_t* newoff;      // per bucket: pool offset of the grown sub-directory
+  uint64_t* gsh;         // [2][kGShards] grant shard words by batch parity (kGStride apart)
+  uint4* gsplit;         // [2][kGShards][gcap] the requested splits by segment offset in their shard:
+                         // {request word, w | i << 14 | entry << 20, pool offset, nr | need << 8}
+  uint32_t gcap;         // splits per shard (kSplitCap x the shard's buckets)
+  uint32_t* act;         // [2^p1] buckets with requests (k_split -> k_apply_parked)
+  uint32_t* fbl;         // [2^p1max] per bucket: bit 0 k_apply_fast declined it (-> k_apply_fb), bits 1+ declines so far
+  uint32_t* hint;        // device-mapped pinned word: k_apply_parked leaves the segment count after
+                         // this batch's grants there (host hint)
+  uint32_t mode;         // (launcher) k_apply: 0 first pass, 1 parked-op pass, 2 parked-op pass without
+                         // split requests (the last before the final pass)
   // worklists: the passes after k_apply visit only the buckets that have work
-  uint32_t* fin;     // [2][2^p1] by batch parity: buckets for the final pass
-  uint32_t par;      // this batch's parity
-  uint32_t gate_tag; // mixed batches: != 0 lets the insert-only apply passes run unless ctl->pget == gate_tag
-  // gated mixed batches: the host expects the mixed passes to stay gated off
-  // (no recent batch ran them, mseen) and launches them on small looping
-  // grids, so their exit costs less; mseen: the host-mapped word the first
-  // mixed pass stamps with gate_tag when it runs
-  uint32_t mixed_small;
-  uint32_t* mseen;
+  uint32_t* fin;         // [2][2^p1] by batch parity: k_bucket's worklist (count: ctl->nfin[par])
+  uint32_t par;          // this batch's parity
+  // mixed batches: both apply variants are launched and exactly one runs.
+  // gate 1 (MIXED kernels) runs iff ctl->pget == gate_tag (k_mixed_get left
+  // a Get pending), gate 2 (the insert-only kernels) iff not; 0: always.
+  // gate: (launcher); gate_tag: != 0 for a gated mixed batch
+  uint32_t gate, gate_tag;
+  uint32_t* mseen;       // host-mapped: k_apply<true> stores gate_tag when it runs (BucketLaunch::mixed_small)
+};
+// what the host-side launch decisions read and the kernels do not
+struct BucketLaunch {
+  BucketArgs a;
   uint32_t wide;     // the lean first pass in its wide variant (k_apply_wide: sub-directories up to 128 entries)
   uint32_t fb;       // launch k_apply_fb after it (else k_apply_parked takes the declined buckets)
   uint32_t cp;       // coarse partition (sbb == 3): the lean first pass is k_apply_fast_cp
-  uint32_t* hint;    // device-mapped pinned word: k_apply_parked leaves the segment count there (host hint)
-  uint32_t ramp = 0;  // the table still ramps (p1 < p1max) or is small for the batch: the larger grids
+  uint32_t ramp;     // the table still ramps (p1 < p1max) or is small for the batch: the larger grids
+  // gated mixed batches: the host expects the mixed passes to stay gated off
+  // (no recent batch ran them, a.mseen) and launches them on small looping
+  // grids, so their exit costs less
+  uint32_t mixed_small;
+  uint64_t* split_stamps;  // debug: 8 stamps for each of the first kSplitStamps splits, or null
 };
-constexpr uint32_t kSplitStamps = 8192;
-// Split requests are granted through kGShards pairs of counters, one per XCD
-// (bucket w -> shard w % 8, the XCD its first-pass wave runs on), each word
-// on a 128-B line of its own: {child segments [0,32) | requesting buckets
-// [32,64)} and the sub-directory pool entries requested in this batch.  A
-// contended single word serializes at ~88 atomics/us, far below the rate of
-// a split-heavy batch's ~8k requests.
-constexpr uint32_t kGShards = 8;
-constexpr uint32_t kGStride = 32;  // u64 words per shard: the segment word at 0, the pool word at 16
-constexpr uint32_t kChunkWave = 256;  // ops per k_apply / k_bucket wave chunk (mean load: 128)
-constexpr uint32_t kSplitCap = 64;    // split requests per directory bucket and round
-// per-bucket cumulative counters: lines, waited, splits, split loss, runs,
-// rounds, {max rounds | max local depth << 16 | growths << 32}, spare
-constexpr int kWStat = 8;
 // k_apply: mode 0 = first pass over the batch's records, 1 = pass over the
 // parked ops (after a split round); final: k_bucket (inline splits, the rest)
 void launch_apply(const BucketLaunch& L, uint32_t mode, hipStream_t s);
-// the lean first pass is on (PMDFC_FAST_APPLY=0 turns it off: A/B)
-bool fast_first_pass();
 // k_apply_fb after the lean first pass (insert-only batches; nothing otherwise)
 void launch_apply_fallback(const BucketLaunch& L, hipStream_t s);
 void launch_final(const BucketLaunch& L, hipStream_t s);
@@ -231,26 +265,53 @@ void launch_final(const BucketLaunch& L, hipStream_t s);
 // a touched list): every listed partition bucket's directory buckets through
 // the final pass, records walked in batch order (k_medium)
 void launch_medium(const BucketLaunch& L, const uint32_t* touched, hipStream_t s);
-// the persistent serving kernel of the per-op front-end (k_serve, one wave)
-struct ServeLaunch {
-  const pmdfc_serve_req* req;  // device mappings of the host rings
-  pmdfc_serve_resp* resp;
-  pmdfc_serve_ctl* ctl;
-  uint64_t ring_size, head0;
-  uint8_t* cbf;
-  uint64_t cbf_m;
-  uint32_t cbf_k;
-  uint32_t nwaves;  // 0/1: one wave from head0; else wave w serves ring w from ctl[w].head
-};
-void launch_serve(const BucketLaunch& L, const ServeLaunch& V, hipStream_t s);
-// a whole batch of n <= kChunkWave ops in one launch (k_mixed_small); ops ==
-// null: insert-only.  L.st / L.vout are the outputs; inputs may be host-mapped
+// a whole batch of n <= kChunkWave ops in one launch (k_mixed_small, k_mixed_tiny
+// up to 64); ops == null: insert-only.  a.st / a.vout are the outputs; inputs
+// may be host-mapped
 void launch_mixed_small(const BucketLaunch& L, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                         hipStream_t s);
+
+// k_split: one wave per entry of the split list the apply pass granted (a
+// fixed grid looping over ctl->nsplit[par] entries; denied entries are ~0).
+// Built from the batch's BucketArgs (bucket.hip split_args).
+struct SplitArgs {
+  uint32_t par;        // the batch's parity: its grant shards
+  uint32_t pfix;       // small sub-directories grow in their fixed slots
+  uint64_t* stamps;    // BucketLaunch::split_stamps
+  const uint64_t* gsh;
+  const uint4* gsplit;
+  uint32_t gcap;
+  uint32_t* act;       // out: the buckets with requests (k_apply_parked's worklist)
+  uint32_t* gbase;     // out, per bucket: first child id, grants, pool offset, sub-directory bits
+  uint32_t* ngrant;
+  uint32_t* newoff;
+  uint32_t* need;
+  uint32_t max_segments, pool_cap;
+  ulonglong2* pairs;
+  uint32_t* occ;
+  uint8_t* ldep;
+  DevCtl* ctl;
+  const uint32_t* reqop;  // batch position of each request's insert (drop log)
+  ulonglong2* drops;      // the drop log, or null
+  uint32_t team_max;      // split lists up to this long go by teams of four waves (PMDFC_SPLIT_TEAM_MAX)
+};
 // one split round: split every segment the apply pass granted (it hands out
 // child ids / sub-directory space itself), one wave each (k_split)
-// insert-only batches: the split round and the last parked pass in one launch
 void launch_split_round(const BucketLaunch& L, hipStream_t s);
+
+// the persistent serving kernel of the per-op front-end (k_serve, a wave per ring)
+struct ServeArgs {
+  BucketArgs a;                 // the engine at launch (st / vout: 64-entry device scratch)
+  const pmdfc_serve_req* req;   // device mappings of the host rings (wave w: places w * ring_size ...)
+  pmdfc_serve_resp* resp;
+  pmdfc_serve_ctl* ctl;         // one per wave
+  uint64_t ring_size, head0;    // head0: one wave's first place; several waves start at their ctl->head
+  uint32_t nwaves;              // 1: one wave from head0; else wave w serves ring w from ctl[w].head
+  uint8_t* cbf;                 // counting BF counters, or null
+  uint64_t cbf_m;
+  uint32_t cbf_k;
+};
+void launch_serve(const ServeArgs& sa, hipStream_t s);
 
 // ubench.hip
 void launch_gather64(const void* buf, uint64_t nlines, const uint32_t* table, uint32_t tmask,

@@ -9,6 +9,7 @@
 // in batch order by one lane, segments in parallel.
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "knobs.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1097,24 +1098,6 @@ __global__ __launch_bounds__(256) void k_bounds(const uint32_t* __restrict__ sor
 // ------------------------------------------------------------------ launchers
 #define GRID(n, per) dim3((unsigned)(((n) + (per)-1) / (per)))
 
-// A/B knob: 0 = no speculative second-line load for even home lines
-static uint32_t get_p2() {
-  static const uint32_t v = [] {
-    const char* e = getenv("PMDFC_GET_P2");
-    return (e && e[0] == '0') ? 0u : 1u;
-  }();
-  return v;
-}
-
-static int get_unroll() {
-  static int u = [] {
-    const char* e = getenv("PMDFC_GET_UNROLL");
-    const int v = e ? atoi(e) : 2;
-    return (v == 1 || v == 2 || v == 4) ? v : 2;
-  }();
-  return u;
-}
-
 // ---- flat directory for pure-Get batches (one L2 lookup per Get instead of
 // header + sub-directory)
 __global__ __launch_bounds__(1024) void k_flat_bits(const uint64_t* __restrict__ hdr, uint32_t nb,
@@ -1152,33 +1135,26 @@ void launch_flatten(const uint64_t* hdr, const uint32_t* pool, uint32_t p1, uint
                      (const uint32_t*)bits);
 }
 
-static uint64_t get_grid_cap() {
-  static const uint64_t v = [] {
-    const char* e = getenv("PMDFC_GET_GRID");
-    return e ? strtoull(e, nullptr, 0) : 0ull;
-  }();
-  return v;
-}
-
 void launch_get(bool count, const uint64_t* keys, uint64_t* vout, uint8_t* st, uint64_t n,
                 Geo g, const ulonglong2* pairs, uint32_t* partials, hipStream_t s) {
   if (!n) return;
-  const int U = get_unroll();
+  const ProcessKnobs& K = process_knobs();
+  const int U = K.get_unroll;
   if (U > 1) {
     const uint64_t quads = (n + U - 1) / U;
     // a launch of several batches' Gets (pmdfc_cceh_get_batches) caps its
     // grid (PMDFC_GET_GRID blocks, 0: none) and loops
-    const uint64_t want = (quads + 63) / 64, cap = count ? 0 : get_grid_cap();  // (COUNT: a partial per block)
+    const uint64_t want = (quads + 63) / 64, cap = count ? 0 : K.get_grid;  // (COUNT: a partial per block)
     const uint64_t nblk = cap && want > cap ? cap : want;
     const uint32_t rounds = (uint32_t)((want + nblk - 1) / nblk);
     const dim3 grid((unsigned)nblk);
 #define LG(UU)                                                                               \
   if (count)                                                                                 \
     hipLaunchKernelGGL((k_get_u<UU, true>), grid, dim3(256), 0, s, keys, vout, st, n, g, pairs, \
-                       partials, get_p2(), rounds);                                          \
+                       partials, K.get_p2, rounds);                                          \
   else                                                                                       \
     hipLaunchKernelGGL((k_get_u<UU, false>), grid, dim3(256), 0, s, keys, vout, st, n, g, pairs, \
-                       partials, get_p2(), rounds);
+                       partials, K.get_p2, rounds);
     if (U == 2) {
       LG(2)
     } else {
@@ -1203,21 +1179,12 @@ void launch_mixed_prep(const uint8_t* ops, const uint64_t* keys, uint8_t* st, ui
 
 // Gets per quad issued together: 2 (configs 4 / 3: U=4 3.91 / 5.76, U=2
 // 3.95 / 5.96, U=1 3.97 / 5.94 Gops/s); PMDFC_MG_U overrides (A/B)
-static int mg_u() {
-  static const int U = [] {
-    const char* e = getenv("PMDFC_MG_U");
-    const int v = e ? atoi(e) : 2;
-    return (v == 1 || v == 4) ? v : 2;
-  }();
-  return U;
-}
-
 void launch_mixed_get_iset(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
                            uint64_t n, Geo g, const ulonglong2* pairs, const uint64_t* iset, uint64_t imask,
                            const uint32_t* ipos, const uint32_t* icnt, uint8_t* early, uint32_t* elink, DevCtl* ctl,
                            uint32_t tag, uint32_t* icount, uint32_t ups, uint32_t* hint_ins, hipStream_t s) {
   if (!n) return;
-  const int U = mg_u();
+  const int U = process_knobs().mg_u;
 #define MG(UU)                                                                                             \
   hipLaunchKernelGGL(k_mixed_get_iset<UU>, GRID(n, 256), dim3(256), 0, s, ops, keys, st, vout, n, g, pairs, iset, \
                      imask, ipos, icnt, early, elink, ctl, tag, icount, ups, hint_ins)
@@ -1231,7 +1198,7 @@ void launch_mixed_get(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uin
                       uint64_t n, Geo g, const ulonglong2* pairs, uint8_t* early, uint32_t* islot, uint32_t* jbits,
                       DevCtl* ctl, uint32_t* loss0, uint32_t tag, uint32_t* icount, uint32_t ups, hipStream_t s) {
   if (!n) return;
-  const int U = mg_u();
+  const int U = process_knobs().mg_u;
 #define MG(UU)                                                                                              \
   hipLaunchKernelGGL(k_mixed_get<UU>, GRID(n, 256), dim3(256), 0, s, ops, keys, st, vout, n, g, pairs, early, \
                      islot, jbits, ctl, loss0, tag, icount, ups)

@@ -43,7 +43,7 @@ def get(r):
 us = timeit(get)
 get(5)
 ok = bool((so == P.ST_HIT).all()) and torch.equal(vo, keys[5 * B:6 * B])
-print(f"Get (pipe {os.environ.get('PMDFC_GET_PIPE', '1')}, U {os.environ.get('PMDFC_GET_UNROLL', '2')}): "
+print(f"Get (U {os.environ.get('PMDFC_GET_UNROLL', '2')}): "
       f"{us:7.1f} us per 1M Gets  ok={ok}  lines/get {t.stats().get('get_lines', 'n/a')}", flush=True)
 if os.environ.get("GATHER", "0") != "1":
     sys.exit(0)
