@@ -125,7 +125,10 @@ const char* pmdfc_last_error(void);
 /* ---- lifecycle ------------------------------------------------------ */
 int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out);
 int pmdfc_cceh_destroy(pmdfc_cceh_t* t);
-/* back to the freshly created state (all keys dropped) */
+/* back to the freshly created state (all keys dropped).  The reset is ordered
+ * on `stream` and does no host sync: it runs after the work already queued
+ * there, and a later call on this engine must use that stream or wait for it
+ * (an event, a stream sync) -- on another stream it may run before the reset. */
 int pmdfc_cceh_reset(pmdfc_cceh_t* t, void* stream);
 
 /* ---- batched ops on device pointers --------------------------------- */

@@ -172,12 +172,10 @@ struct pmdfc_cceh {
   pmdfc_cceh_config_t cfg{};
   int dev = 0;
   uint32_t D0 = 1, sbits = 0, shard = 0;
-  uint32_t p1 = 0;        // directory bucket bits (grows to p1max as the table deepens)
+  uint32_t p1 = 0;        // directory bucket bits (grows to p1max as the table deepens: rebucket_now)
   uint32_t p1_init = 0, p1max = 0;
-  uint32_t sbb = 0;       // of which sub-bucket bits (partition buckets = 2^(p1 - sbb)); per batch (batch_geometry)
-  uint32_t cp = 0;        // this batch uses the coarse partition (sbb == kCpSbb, k_apply_fast_cp)
-  uint32_t g_wide = 0, g_fb = 0;  // this batch's lean pass variant (batch_geometry)
-  uint32_t clean_sbb = ~0u;  // the current record buffer's cursors are zero for this geometry (~0: all zero)
+  // (what ONE batch's launches are filled from is a BatchPlan, not kept here)
+  uint32_t clean_sbb = ~0u;  // the next record buffer's cursors are zero for a batch of this sbb (~0: all zero)
   size_t cblk = 0;        // cursor block per record buffer, sized for p1max
   uint64_t* hdr_tmp = nullptr;  // re-bucketing: the old headers
   uint32_t* h_depth = nullptr;  // pinned: k_min_ldep's result
@@ -218,12 +216,11 @@ struct pmdfc_cceh {
   DevCtl* hctl = nullptr;  // pinned mirror (stats / dump only)
 
   // partition records
-  uint32_t cap = 0;  // record slots per partition bucket region
   ulonglong2* rkv = nullptr;   // records {key, value}
   uint32_t* rop = nullptr;
   uint16_t* robk = nullptr;    // overflow records' bucket
   uint64_t nrec = 0;           // record slots per record buffer
-  uint32_t* cursor = nullptr;  // 2 x (2^(p1 - sbb) region cursors + 1 overflow cursor), by batch parity
+  uint32_t* cursor = nullptr;  // kRecBufs x (the partition buckets' region cursors + 1 overflow cursor)
   uint64_t* wstat = nullptr;   // per directory bucket counters (summed by stats())
   ulonglong2* wl_kv = nullptr; // parked ops per directory bucket (apply -> final pass)
   uint32_t* wl_op = nullptr;
@@ -252,9 +249,11 @@ struct pmdfc_cceh {
   uint64_t* srv_vout = nullptr;
   uint64_t* stamps = nullptr;  // debug (kn.stamps): [0, 8*nb) k_bucket, then k_part
   // (kn.stamp_rot sets, batch i writing set i % stamp_rot, for a timeline of
-  // consecutive pipelined batches; stamp_cur: this batch's)
-  uint64_t* stamp_cur = nullptr;
+  // consecutive pipelined batches; stamp_last: the set of the last batch
+  // planned, for pmdfc_cceh_debug_stamps -- plan_batch alone writes both)
+  uint64_t* stamp_last = nullptr;
   uint32_t stamp_seq = 0;
+  std::vector<void*> dev_allocs;  // every hipMalloc of create (ALLOC), for destroy
 
   // insert_batches: batch i+1 is partitioned on pstream while batch i is
   // applied on the caller's stream
@@ -319,6 +318,17 @@ static int read_ctl(pmdfc_cceh* t, hipStream_t s) {
   return PMDFC_OK;
 }
 
+// The per-bucket counters (the slots of every bucket geometry so far) and,
+// from them and the control block read_ctl left in hctl, the deepest local
+// depth: stats() sums the rest, dump() needs the depth alone.
+static int read_wstat(pmdfc_cceh* t, std::vector<uint64_t>& ws, uint32_t& max_ld) {
+  ws.resize((size_t)kWStat << t->p1max);
+  HIPCHK(hipMemcpy(ws.data(), t->wstat, ws.size() * 8, hipMemcpyDeviceToHost));
+  max_ld = t->hctl->max_ld;
+  for (size_t i = 6; i < ws.size(); i += kWStat) max_ld = std::max<uint32_t>(max_ld, (uint32_t)((ws[i] >> 16) & 0xFF));
+  return PMDFC_OK;
+}
+
 // per parity: kPartSubs cursors per partition bucket + the overflow cursor,
 // padded to 256 B so both blocks are aligned (one fill kernel per memset)
 static size_t cursor_block(uint32_t npb) { return ((size_t)npb * kPartSubs + 1 + 63) & ~(size_t)63; }
@@ -338,40 +348,95 @@ static uint32_t part_cap(uint32_t max_batch, uint32_t p1, uint32_t sbb) {
   return (uint32_t)((2 * per_sub + 16) * kPartSubs);
 }
 
-static void set_geometry(pmdfc_cceh* t, uint32_t p1) {
-  t->p1 = p1;
-  t->sbb = p1 > kMaxPartBits ? p1 - kMaxPartBits : 0;
-  t->cap = part_cap(t->max_batch, p1, t->sbb);
-  t->cp = 0;
-}
+// One debug stamp set (kn.stamps): 16 words per directory bucket (2^p1max
+// rows, the bucket passes), then 8 per k_part block of a max_batch batch, then
+// 8 for each of the first kSplitStamps splits.
+static uint64_t stamp_part_off(const pmdfc_cceh* t) { return 16ULL << t->p1max; }
+static uint64_t stamp_split_off(const pmdfc_cceh* t) { return stamp_part_off(t) + 8ULL * part_blocks(t->max_batch); }
+static uint64_t stamp_words(const pmdfc_cceh* t) { return stamp_split_off(t) + 8ULL * kSplitStamps; }
 
-// The partition geometry of ONE batch, chosen before its launches are filled:
-// insert-only, non-upsert batches of a table at its bucket resolution whose
+// What ONE batch's launches are filled from, chosen by plan_batch before the
+// batch's first launch (pipe_group keeps a group's plans until their passes).
+struct BatchPlan {
+  uint32_t rb = 0;   // record buffer: records, cursors, k_part overflow
+  uint32_t par = 0;  // batch parity: the bucket passes' per-batch words (grant shards, worklists)
+  uint32_t sbb = 0;  // sub-bucket bits (partition buckets = 2^(p1 - sbb))
+  uint32_t cap = 0;  // record slots per partition bucket region
+  uint32_t cp = 0;   // the coarse partition (sbb == kCpSbb, k_apply_fast_cp)
+  uint32_t wide = 0, fb = 0;   // the lean first pass is the wide one; k_apply_fb is launched
+  uint64_t* stamps = nullptr;  // the batch's debug stamp set, or null
+};
+
+// Insert-only, non-upsert batches of a table at its bucket resolution whose
 // lean pass is the narrow one take the coarse partition (2^(p1 - 3)
 // partition buckets of 8 directory buckets: k_part writes runs of ~8 records
 // per tile and bucket instead of ~1, k_apply_fast_cp stages them per
-// workgroup); the rest the fine one.  A batch whose record buffer's cursors
-// were zeroed for another geometry (the previous batch clears the next
-// buffer's cursors at its own positions) zeroes them all on `s` first
-// (s == null: the caller zeroes them itself).
-static int batch_geometry(pmdfc_cceh* t, bool insert_only, uint64_t n, hipStream_t s, bool zero_cursors = true) {
+// workgroup); the rest the fine one.  The lean pass is the wide one once the
+// table has more segments per bucket than the narrow one's 32-entry
+// sub-directories hold (about 20: a bucket's deepest segment sits ~1.5 levels
+// below the mean).  The count is a hint the device leaves in pinned memory
+// (k_apply_parked), read without a sync, so it may lag the batches in flight:
+// either variant is exact, and each hands the buckets it cannot take to
+// k_apply_fb.  records: the batch has a partition, so it takes the next stamp
+// set, in partition order (k_mixed_small and k_serve have none).
+static BatchPlan plan_batch(pmdfc_cceh* t, bool insert_only, uint64_t n, bool records = true) {
+  BatchPlan b;
+  b.rb = t->rb;
+  b.par = t->parity;
   const uint32_t spb = __atomic_load_n(t->h_hint, __ATOMIC_RELAXED) >> t->p1;  // segments per bucket
-  t->g_wide = spb > kWideSegs ? 1u : 0u;
-  t->g_fb = spb > kFbSegs ? 1u : 0u;
+  b.wide = spb > kWideSegs ? 1u : 0u;
+  b.fb = spb > kFbSegs ? 1u : 0u;
   // records per (partition bucket, sub-region): a sub-region takes the
   // records of ceil(tiles / kPartSubs) tiles; the staging holds kCpPre, so
   // the mean must stay near 2/3 of it (1M ops at p1 = 13: 128)
   const uint64_t tiles = (n + kPartTile - 1) / kPartTile;
   const uint64_t per_sub = t->p1 > kCpSbb ? (((tiles + kPartSubs - 1) / kPartSubs) * kPartTile) >> (t->p1 - kCpSbb) : ~0ull;
-  const bool cp = insert_only && !t->upsert && !t->g_wide && t->p1 == t->p1max && per_sub <= 128 &&
+  const bool cp = insert_only && !t->upsert && !b.wide && t->p1 == t->p1max && per_sub <= 128 &&
                   process_knobs().cp && process_knobs().fast_apply;
-  const uint32_t sbb = cp ? kCpSbb : (t->p1 > kMaxPartBits ? t->p1 - kMaxPartBits : 0);
-  t->cp = cp ? 1u : 0u;
-  t->sbb = sbb;
-  t->cap = part_cap(t->max_batch, t->p1, sbb);
-  if (zero_cursors && t->clean_sbb != ~0u && t->clean_sbb != sbb)
-    HIPCHK(hipMemsetAsync(t->cursor + (size_t)t->rb * t->cblk, 0, t->cblk * sizeof(uint32_t), s));
+  b.cp = cp ? 1u : 0u;
+  b.sbb = cp ? kCpSbb : (t->p1 > kMaxPartBits ? t->p1 - kMaxPartBits : 0);
+  b.cap = part_cap(t->max_batch, t->p1, b.sbb);
+  if (records && t->stamps)
+    b.stamps = t->stamp_last = t->stamps + (uint64_t)(t->stamp_seq++ % t->kn.stamp_rot) * stamp_words(t);
+  return b;
+}
+
+// (the batch before zeroed this buffer's cursors at its own geometry's
+// positions: a one-batch path of another geometry zeroes the whole block)
+static int zero_stale_cursors(pmdfc_cceh* t, const BatchPlan& b, hipStream_t s) {
+  if (t->clean_sbb != ~0u && t->clean_sbb != b.sbb)
+    HIPCHK(hipMemsetAsync(t->cursor + (size_t)b.rb * t->cblk, 0, t->cblk * sizeof(uint32_t), s));
   return PMDFC_OK;
+}
+
+// How each path leaves the handle (finish_batch; every path also invalidates
+// the flattened Get directory):
+//   flip   the batch parity flips.  Not after k_medium (the final pass, splits
+//          inline): it never touches the per-batch words, and only a general
+//          batch's first pass clears the other parity's, so a flip would hand
+//          the next general batch the stale words of the one before this.
+//   next   the record buffer ring advances (the batch had a partition).
+//   clean  its first pass (or k_medium) zeroed the next buffer's cursors at its
+//          own positions: clean_sbb is its sbb.  Pipelined partitions zero
+//          whole blocks instead; pipe_end zeroes the next and sets ~0u.
+//   count  batches += 1; a general batch is a sub-batch of a call that counts
+//          once itself (insert_ramped, pmdfc_cceh_mixed).
+enum BatchPath { kPathSmall, kPathMedium, kPathGeneral, kPathPiped, kPathServe };
+static constexpr struct { bool flip, next, clean, count; } kFinish[] = {
+    {false, false, false, true},   // kPathSmall
+    {false, true, true, true},     // kPathMedium
+    {true, true, true, false},     // kPathGeneral (insert_one, mixed_one)
+    {true, true, false, true},     // kPathPiped (pipe_batch, pipe_group)
+    {false, false, false, false},  // kPathServe
+};
+
+static void finish_batch(pmdfc_cceh* t, const BatchPlan& b, BatchPath path) {
+  const auto& f = kFinish[path];
+  if (f.flip) t->parity = b.par ^ 1u;
+  if (f.next) t->rb = (b.rb + 1) % kRecBufs;
+  if (f.clean) t->clean_sbb = b.sbb;
+  if (f.count) t->batches += 1;
+  t->flat_valid = false;
 }
 
 // A table created small (CCEH_hybrid(2): 2 segments, so 2 directory buckets)
@@ -406,7 +471,7 @@ static int rebucket_now(pmdfc_cceh* t, hipStream_t s) {
   HIPCHK(hipMemcpyAsync(t->hdr_tmp, t->hdr, sizeof(uint64_t) << t->p1, hipMemcpyDeviceToDevice, s));
   launch_rebucket(t->hdr_tmp, t->hdr, t->p1, target, s);
   HIPCHK(hipGetLastError());
-  set_geometry(t, target);
+  t->p1 = target;
   t->flat_valid = false;
   t->rebuckets += 1;
   return PMDFC_OK;
@@ -420,6 +485,15 @@ static uint64_t ramp_batch(const pmdfc_cceh* t, uint64_t n) {
   return std::min<uint64_t>(n, std::max<uint64_t>(K.ramp_ops << t->p1, K.ramp_min));
 }
 
+// empty the mixed batches' key set (32 MB of fills at 1M-op batches, ~20 us)
+static int clear_key_set(pmdfc_cceh* t, hipStream_t s) {
+  HIPCHK(hipMemsetAsync(t->iset, 0xFF, (t->imask + 1) * sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(t->icnt, 0, (t->imask + 1) * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(t->ipos, 0xFF, (t->imask + 1) * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(t->jbits, 0, kJoinWords * sizeof(uint32_t), s));
+  return PMDFC_OK;
+}
+
 static int init_state(pmdfc_cceh* t, hipStream_t s) {
   const uint32_t n0 = 1u << (t->D0 - t->sbits);
   // (no earlier rebucket_now copy may land after the seed below: the event
@@ -431,16 +505,13 @@ static int init_state(pmdfc_cceh* t, hipStream_t s) {
   // the mixed batches' key set is empty between batches (each batch's verify
   // pass empties the slots it used), so a reset leaves it alone -- unless it
   // is not known empty (a new engine, or a batch that stopped between its prep
-  // and verify passes): then emptied here (32 MB of fills at 1M-op batches,
-  // ~20 us of a reset the bench pays every step)
+  // and verify passes): then emptied here (a cost the bench's reset at
+  // every step must not pay)
   if (t->iset_dirty) {
-    HIPCHK(hipMemsetAsync(t->iset, 0xFF, (t->imask + 1) * sizeof(uint64_t), s));
-    HIPCHK(hipMemsetAsync(t->icnt, 0, (t->imask + 1) * sizeof(uint32_t), s));
-    HIPCHK(hipMemsetAsync(t->ipos, 0xFF, (t->imask + 1) * sizeof(uint32_t), s));
-    HIPCHK(hipMemsetAsync(t->jbits, 0, kJoinWords * sizeof(uint32_t), s));
+    if (int rc = clear_key_set(t, s)) return rc;
     t->iset_dirty = false;
   }
-  set_geometry(t, t->p1_init);
+  t->p1 = t->p1_init;
   const uint32_t region = kFixedSlot << t->p1max;  // the fixed slots come first in the pool
   const uint32_t db0 = t->D0 - t->sbits - t->p1;
   const uint32_t fixed = (t->p1 == t->p1max && db0 <= kFixedBits) ? 1u : 0u;
@@ -470,32 +541,39 @@ static int init_state(pmdfc_cceh* t, hipStream_t s) {
   return PMDFC_OK;
 }
 
-// The bucket passes' arguments for the batch of record buffer t->rb (B{}: the
-// launchers' a.mode / a.gate, the gated mixed batches' gate_tag / mseen /
-// mixed_small and the drop log stay zero unless the caller sets them).
-static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8_t* st,
-                               uint64_t* vout, bool mixed) {
-  const uint32_t npb = 1u << (t->p1 - t->sbb);
-  const uint32_t p = t->rb;
-  BucketArgs& a = L.a;
-  a.n = n;
+// The view of the plan's record buffer that PartArgs and BucketArgs share:
+// the records with their overflow tags, the partition buckets' cursors with
+// the overflow cursor after them, and the region sizes.
+template <class Args>
+static void fill_record_view(const pmdfc_cceh* t, const BatchPlan& b, Args& a) {
+  const uint32_t p = b.rb, pbits = t->p1 - b.sbb;
   a.rkv = t->rkv + p * t->nrec;
   a.rop = t->rop + p * t->nrec;
   a.robk = t->robk + (size_t)p * t->max_batch;
-  a.chunk = (t->kn.chunk == 0 || t->kn.chunk > kChunkWave) ? kChunkWave : t->kn.chunk;
-  a.cap = t->cap;
-  a.capx = t->cap / kPartSubs;
-  a.ovf_base = (uint64_t)t->cap << (t->p1 - t->sbb);
   a.cursor = t->cursor + (size_t)p * t->cblk;
-  a.ovf = a.cursor + (size_t)npb * kPartSubs;
-  a.cursor_next = t->cursor + (size_t)((p + 1) % kRecBufs) * t->cblk;
-  a.ovf_next = a.cursor_next + (size_t)npb * kPartSubs;
+  a.ovf = a.cursor + ((size_t)kPartSubs << pbits);
+  a.cap = b.cap;
+  a.capx = b.cap / kPartSubs;
+  a.ovf_base = (uint64_t)b.cap << pbits;
+}
+
+// The bucket passes' arguments for the batch of plan b (B{}: the launchers'
+// a.mode / a.gate, the gated mixed batches' gate_tag / mseen / mixed_small and
+// the drop log stay zero unless the caller sets them).
+static void fill_bucket_launch(const pmdfc_cceh* t, const BatchPlan& b, BucketLaunch& L, uint64_t n, uint8_t* st,
+                               uint64_t* vout, bool mixed) {
+  BucketArgs& a = L.a;
+  a.n = n;
+  fill_record_view(t, b, a);
+  a.chunk = (t->kn.chunk == 0 || t->kn.chunk > kChunkWave) ? kChunkWave : t->kn.chunk;
+  a.cursor_next = t->cursor + (size_t)((b.rb + 1) % kRecBufs) * t->cblk;
+  a.ovf_next = a.cursor_next + (a.ovf - a.cursor);
   a.clear_next = 1;
   a.hdr = t->hdr;
   a.pool = t->pool;
   a.pool_cap = (uint32_t)t->pool_cap;
   a.p1 = t->p1;
-  a.sbb = t->sbb;
+  a.sbb = b.sbb;
   a.sbits = t->sbits;
   a.shard = t->shard;
   a.pfix = t->p1 == t->p1max ? 1u : 0u;
@@ -513,7 +591,7 @@ static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8
   a.wl_kv = t->wl_kv;
   a.wl_op = t->wl_op;
   a.wl_n = t->wl_n;
-  a.stamps = t->stamp_cur;
+  a.stamps = b.stamps;
   a.req = t->req;
   a.reqop = t->reqop;
   a.drops = nullptr;  // (mixed batches with early answers set it)
@@ -527,18 +605,12 @@ static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8
   a.act = t->act;
   a.fin = t->fin;
   a.fbl = t->fbl;
-  a.par = t->parity;
-  // the lean first pass in its wide variant once the table has more segments
-  // per bucket than the narrow one's 32-entry sub-directories hold (about 20:
-  // a bucket's deepest segment sits ~1.5 levels below the mean).  The count is
-  // a hint the device leaves in pinned memory (k_apply_parked), read without
-  // a sync, so it may lag the batches in flight: either variant is exact, and
-  // each hands the buckets it cannot take to k_apply_fb.
+  a.par = b.par;
   a.hint = t->d_hint;
-  L.wide = t->g_wide;  // (batch_geometry)
-  L.fb = t->g_fb;
-  L.cp = t->cp;
-  L.split_stamps = t->stamp_cur ? t->stamp_cur + (16ULL << t->p1max) + 8ULL * part_blocks(t->max_batch) : nullptr;
+  L.wide = b.wide;
+  L.fb = b.fb;
+  L.cp = b.cp;
+  L.split_stamps = b.stamps ? b.stamps + stamp_split_off(t) : nullptr;
   // the larger grids of the passes after the first while the table ramps,
   // or is still small for the batch (more than 32 ops per segment: windows
   // fill within the batch, the final pass has work): the CCEH_hybrid(2)
@@ -550,21 +622,11 @@ static void fill_bucket_launch(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8
   }
 }
 
-// the launches without records (k_mixed_small, k_serve): no phase stamps either
-static void fill_bucket_launch_direct(pmdfc_cceh* t, BucketLaunch& L, uint64_t n, uint8_t* st, uint64_t* vout) {
-  fill_bucket_launch(t, L, n, st, vout, true);
-  L.a.stamps = nullptr;
-}
-
-static uint64_t stamp_words(const pmdfc_cceh* t) {
-  return 16ULL * (1ULL << t->p1max) + 8ULL * part_blocks(t->max_batch) + 8ULL * kSplitStamps;
-}
-
-// k_part's arguments for the batch of record buffer t->rb (P{}: the medium
-// batches' init / vout / touched and the mixed batches' join group stay zero
-// unless the caller sets them); kvs: 1 for key / value arrays, 2 for records
-static void fill_part_launch(pmdfc_cceh* t, PartArgs& a, const uint8_t* ops, const uint64_t* keys,
-                             const uint64_t* vin, uint32_t kvs, uint8_t* st, uint64_t n) {
+// k_part's arguments for the batch of plan b (P{}: the medium batches' init /
+// vout / touched and the mixed batches' join group stay zero unless the
+// caller sets them); kvs: 1 for key / value arrays, 2 for records
+static void fill_part_launch(const pmdfc_cceh* t, const BatchPlan& b, PartArgs& a, const uint8_t* ops,
+                             const uint64_t* keys, const uint64_t* vin, uint32_t kvs, uint8_t* st, uint64_t n) {
   a.keys = keys;
   a.vin = vin;
   a.kvs = kvs ? kvs : 1u;
@@ -573,21 +635,11 @@ static void fill_part_launch(pmdfc_cceh* t, PartArgs& a, const uint8_t* ops, con
   a.n = n;
   a.sbits = t->sbits;
   a.shard = t->shard;
-  a.pbits = t->p1 - t->sbb;
-  a.sbb = t->sbb;
-  a.cap = t->cap;
-  a.capx = t->cap / kPartSubs;
-  a.ovf_base = (uint64_t)t->cap << a.pbits;
-  const uint32_t p = t->rb, npb = 1u << a.pbits;
-  a.rkv = t->rkv + p * t->nrec;
-  a.rop = t->rop + p * t->nrec;
-  a.robk = t->robk + (size_t)p * t->max_batch;
-  a.cursor = t->cursor + (size_t)p * t->cblk;
-  a.ovf = a.cursor + (size_t)npb * kPartSubs;
-  a.povf = t->povf + (size_t)p * part_blocks(t->max_batch) * (1u << kMaxPartBits);
-  // (each batch's partition comes first: it takes the batch's stamp set)
-  t->stamp_cur = t->stamps ? t->stamps + (uint64_t)(t->stamp_seq++ % t->kn.stamp_rot) * stamp_words(t) : nullptr;
-  a.stamps = t->stamp_cur ? t->stamp_cur + (16ULL << t->p1max) : nullptr;
+  a.pbits = t->p1 - b.sbb;
+  a.sbb = b.sbb;
+  fill_record_view(t, b, a);
+  a.povf = t->povf + (size_t)b.rb * part_blocks(t->max_batch) * (1u << kMaxPartBits);
+  a.stamps = b.stamps ? b.stamps + stamp_part_off(t) : nullptr;
 }
 
 // The bucket passes of one insert / mixed batch, all on the stream: a first
@@ -671,9 +723,7 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   t->kn = CreateKnobs::read();
   t->p1max = t->kn.p1max >= 0 ? (uint32_t)t->kn.p1max : std::min<uint32_t>(p1t, kMaxP1);
   t->p1_init = std::min<uint32_t>(t->p1max, Dl0);
-  // k_part partitions into at most 2^kMaxPartBits buckets; finer directory
-  // buckets share a partition bucket (sub-buckets)
-  set_geometry(t, t->p1_init);
+  t->p1 = t->p1_init;
   uint64_t ms = cfg->max_segments;
   if (ms == 0) {
     size_t fr = 0, tot = 0;
@@ -689,11 +739,13 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
                                         ((uint64_t)kFixedSlot << t->p1max), 0xFFFFFFF0ULL);
   // every per-bucket array is sized for p1max
   const uint64_t nb = 1ULL << t->p1max;
+  // k_part partitions into at most 2^kMaxPartBits buckets; finer directory
+  // buckets share a partition bucket (sub-buckets)
   uint64_t nrec = 0;
   for (uint32_t q = t->p1_init; q <= t->p1max; ++q) {
     const uint32_t sq = q > kMaxPartBits ? q - kMaxPartBits : 0;
     nrec = std::max<uint64_t>(nrec, ((uint64_t)part_cap(t->max_batch, q, sq) << (q - sq)) + t->max_batch);
-    if (q > kCpSbb)  // (the coarse partition of batch_geometry)
+    if (q > kCpSbb)  // (the coarse partition of plan_batch)
       nrec = std::max<uint64_t>(nrec, ((uint64_t)part_cap(t->max_batch, q, kCpSbb) << (q - kCpSbb)) + t->max_batch);
   }
   t->nrec = nrec;
@@ -701,8 +753,8 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
     const uint32_t sq = t->p1max > kMaxPartBits ? t->p1max - kMaxPartBits : 0;
     t->cblk = cursor_block(1u << (t->p1max - sq));
   }
-  const uint64_t nblk = part_blocks(t->max_batch);
   hipError_t e;
+  // (every allocation is recorded on the handle: destroy frees that list)
 #define ALLOC(p, bytes)                                                   \
   do {                                                                    \
     e = hipMalloc(&(p), (bytes));                                         \
@@ -710,6 +762,7 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
       pmdfc_cceh_destroy(t);                                              \
       return fail(PMDFC_ERR_NOMEM, "hipMalloc " #p, e);                   \
     }                                                                     \
+    t->dev_allocs.push_back(p);                                           \
   } while (0)
   ALLOC(t->pairs, ms * kSlots * sizeof(ulonglong2));
   ALLOC(t->occ, ms * 32 * sizeof(uint32_t));
@@ -770,9 +823,9 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   ALLOC(t->srv_st, 64);
   ALLOC(t->srv_vout, 64 * sizeof(uint64_t));
   if (t->kn.stamps) {
-    ALLOC(t->stamps, t->kn.stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t));
-    HIPCHK(hipMemset(t->stamps, 0, t->kn.stamp_rot * (16 * nb + 8 * nblk + 8ULL * kSplitStamps) * sizeof(uint64_t)));
-    t->stamp_cur = t->stamps;
+    const uint64_t bytes = t->kn.stamp_rot * stamp_words(t) * sizeof(uint64_t);
+    ALLOC(t->stamps, bytes);
+    HIPCHK(hipMemset(t->stamps, 0, bytes));
   }
 #undef ALLOC
   {
@@ -829,11 +882,7 @@ int pmdfc_cceh_destroy(pmdfc_cceh_t* t) {
   DevGuard g(t->dev);
   (void)hipDeviceSynchronize();
   t->timing.flush_closed();
-  void* ptrs[] = {t->upos, t->pairs, t->occ, t->ldep, t->iset, t->ipos, t->islot, t->icnt, t->icount, t->jbits, t->early, t->elink, t->loss0, t->hdr, t->pool, t->ctl, t->rkv,
-                  t->rop, t->robk, t->cursor, t->wstat, t->wl_kv, t->wl_op, t->wl_n, t->partials, t->popc, t->stamps,
-                  t->req, t->reqop, t->drops, t->gsh, t->gsplit, t->act, t->touched, t->povf, t->gflat, t->gflat_bits, t->need, t->gbase, t->ngrant, t->newoff, t->fin, t->fbl, t->hdr_tmp, t->minld, t->srv_st, t->srv_vout};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  for (void* p : t->dev_allocs) (void)hipFree(p);
   if (t->hctl) (void)hipHostFree(t->hctl);
   if (t->h_depth) (void)hipHostFree(t->h_depth);
   if (t->h_hint) (void)hipHostFree(t->h_hint);
@@ -930,14 +979,13 @@ static int small_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
                      uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
   int rc = rebucket_now(t, s);  // (a table coarser than p1max: one sync, as the general path)
   if (rc) return rc;
-  if ((rc = batch_geometry(t, false, n, s, false))) return rc;  // (no records)
+  const BatchPlan b = plan_batch(t, false, n, false);  // (no records)
   BucketLaunch B{};
-  fill_bucket_launch_direct(t, B, n, st, vout);
+  fill_bucket_launch(t, b, B, n, st, vout, true);
   t->timing.begin(PMDFC_K_PROCESS, s);
   launch_mixed_small(B, ops, keys, vin, s);
   t->timing.end(s);
-  t->batches += 1;
-  t->flat_valid = false;
+  finish_batch(t, b, kPathSmall);
   HIPCHK(hipGetLastError());
   return PMDFC_OK;
 }
@@ -951,39 +999,32 @@ static uint64_t medium_max() { return process_knobs().medium_max; }
 
 static int medium_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin, uint32_t kvs,
                       uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
-  int rc = batch_geometry(t, false, n, s);
-  if (rc) return rc;
+  const BatchPlan b = plan_batch(t, false, n);
+  if (int rc = zero_stale_cursors(t, b, s)) return rc;
   PartArgs P{};
-  fill_part_launch(t, P, ops, keys, vin, kvs, st, n);
+  fill_part_launch(t, b, P, ops, keys, vin, kvs, st, n);
   P.init = ops ? 1u : 0u;
   P.vout = vout;
   P.touched = t->touched;
   BucketLaunch B{};
-  fill_bucket_launch(t, B, n, st, vout, ops != nullptr);
+  fill_bucket_launch(t, b, B, n, st, vout, ops != nullptr);
   t->timing.begin(PMDFC_K_PROCESS, s);
   launch_part(P, s);
   launch_medium(B, t->touched, s);
   t->timing.end(s);
-  // the batch parity stays: k_medium (the final pass, splits inline) never
-  // touches the per-batch words (grant shards, worklists), and only a general
-  // batch's first pass clears the other parity's -- flipping here would hand
-  // the next general batch the stale words of the one before this
-  t->rb = (t->rb + 1) % kRecBufs;
-  t->clean_sbb = t->sbb;  // (k_medium zeroed the next buffer's cursors at its positions)
-  t->batches += 1;
-  t->flat_valid = false;
+  finish_batch(t, b, kPathMedium);
   HIPCHK(hipGetLastError());
   return PMDFC_OK;
 }
 
 static int insert_one(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin, uint32_t kvs, uint8_t* st,
                       uint64_t n, hipStream_t s) {
-  int rc = batch_geometry(t, true, n, s);
-  if (rc) return rc;
+  const BatchPlan b = plan_batch(t, true, n);
+  if (int rc = zero_stale_cursors(t, b, s)) return rc;
   PartArgs P{};
-  fill_part_launch(t, P, nullptr, keys, vin, kvs, st, n);
+  fill_part_launch(t, b, P, nullptr, keys, vin, kvs, st, n);
   BucketLaunch B{};
-  fill_bucket_launch(t, B, n, st, nullptr, false);
+  fill_bucket_launch(t, b, B, n, st, nullptr, false);
   t->timing.begin(PMDFC_K_ROUTE, s);
   // upsert: the lean first pass probes each window itself; the pre-batch
   // probe serves the general pass only when the lean one is off
@@ -993,10 +1034,7 @@ static int insert_one(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   launch_part(P, s);
   run_bucket_passes(t, B, s);
   t->timing.end(s);
-  t->parity ^= 1;
-  t->rb = (t->rb + 1) % kRecBufs;
-  t->clean_sbb = t->sbb;  // (its first pass zeroed the next buffer's cursors at its positions)
-  t->flat_valid = false;
+  finish_batch(t, b, kPathGeneral);
   HIPCHK(hipGetLastError());
   return PMDFC_OK;
 }
@@ -1057,7 +1095,8 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
                       uint64_t n, hipStream_t s, uint32_t k, hipEvent_t input_ready,
                       hipEvent_t output_free = nullptr) {
   hipStream_t P = t->pstream;
-  const uint32_t p = t->rb;
+  const BatchPlan b = plan_batch(t, true, n);
+  const uint32_t p = b.rb;
   // record buffer p's records and cursors were last read by the batch
   // kRecBufs back: with three buffers the partition of batch k + 1 may start
   // as soon as batch k - 2 is applied, so it runs under the bucket passes of
@@ -1066,10 +1105,8 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   if (input_ready) HIPCHK(hipStreamWaitEvent(P, input_ready, 0));
   if (output_free) HIPCHK(hipStreamWaitEvent(P, output_free, 0));  // (the partition writes the statuses)
   HIPCHK(hipMemsetAsync(t->cursor + p * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
-  int rc = batch_geometry(t, true, n, nullptr, false);  // (its cursors: zeroed just above)
-  if (rc) return rc;
   PartArgs PL{};
-  fill_part_launch(t, PL, nullptr, keys, vin, kvs, st, n);
+  fill_part_launch(t, b, PL, nullptr, keys, vin, kvs, st, n);
   hipEvent_t e0 = t->timing.span_begin(P);
   const bool probe = t->upsert && !process_knobs().fast_apply;  // (as insert_one)
   if (probe) {  // the probe reads the table: after the previous batch (ev_done)
@@ -1081,16 +1118,13 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   HIPCHK(hipEventRecord(t->ev_part[p], P));
   HIPCHK(hipStreamWaitEvent(s, t->ev_part[p], 0));
   BucketLaunch B{};
-  fill_bucket_launch(t, B, n, st, nullptr, false);
+  fill_bucket_launch(t, b, B, n, st, nullptr, false);
   B.a.clear_next = 0;  // the next batch's cursors may already be in use
   if (!probe) B.a.upos = nullptr;
   run_bucket_passes(t, B, s);
   t->timing.end(s);
   HIPCHK(hipEventRecord(t->ev_done[p], s));
-  t->batches += 1;
-  t->parity ^= 1;
-  t->rb = (t->rb + 1) % kRecBufs;
-  t->flat_valid = false;
+  finish_batch(t, b, kPathPiped);
   return PMDFC_OK;
 }
 
@@ -1105,47 +1139,30 @@ static int pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
 static int pipe_group(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin, uint8_t* st,
                       const uint64_t* bounds, const uint32_t* idx, uint32_t m, hipStream_t s, uint32_t gi) {
   hipStream_t P = t->pstream;
-  struct Geo1 {
-    uint32_t rb, sbb, cap, cp, wide, fb;
-    uint64_t* stamps;
-  } geo[kRecBufs / 2 > 0 ? kRecBufs / 2 : 1];
+  BatchPlan plans[kRecBufs / 2 > 0 ? kRecBufs / 2 : 1];
   if (gi >= 2) HIPCHK(hipStreamWaitEvent(P, t->ev_gdone[gi & 1u], 0));
   hipEvent_t e0 = t->timing.span_begin(P);
   for (uint32_t j = 0; j < m; ++j) {
     const uint64_t o = bounds[idx[j]], n = bounds[idx[j] + 1] - o;
-    const uint32_t p = t->rb;
-    HIPCHK(hipMemsetAsync(t->cursor + p * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
-    if (int rc = batch_geometry(t, true, n, nullptr, false)) return rc;  // (its cursors: zeroed just above)
+    const BatchPlan& b = plans[j] = plan_batch(t, true, n);
+    HIPCHK(hipMemsetAsync(t->cursor + b.rb * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
     PartArgs PL{};
-    fill_part_launch(t, PL, nullptr, keys + o, vin + o, 1, st + o, n);
+    fill_part_launch(t, b, PL, nullptr, keys + o, vin + o, 1, st + o, n);
     launch_part(PL, P);
-    geo[j] = {p, t->sbb, t->cap, t->cp, t->g_wide, t->g_fb, t->stamp_cur};
-    t->rb = (p + 1) % kRecBufs;
+    finish_batch(t, b, kPathPiped);  // (the handle moves on; the passes below are filled from the plan alone)
   }
   t->timing.span_end(PMDFC_K_ROUTE, e0, P);
   HIPCHK(hipEventRecord(t->ev_gpart[gi & 1u], P));
   HIPCHK(hipStreamWaitEvent(s, t->ev_gpart[gi & 1u], 0));
-  const uint32_t rb_next = t->rb;
   for (uint32_t j = 0; j < m; ++j) {
     const uint64_t o = bounds[idx[j]], n = bounds[idx[j] + 1] - o;
-    t->rb = geo[j].rb;
-    t->sbb = geo[j].sbb;
-    t->cap = geo[j].cap;
-    t->cp = geo[j].cp;
-    t->g_wide = geo[j].wide;
-    t->g_fb = geo[j].fb;
-    t->stamp_cur = geo[j].stamps;
     BucketLaunch B{};
-    fill_bucket_launch(t, B, n, st + o, nullptr, false);
+    fill_bucket_launch(t, plans[j], B, n, st + o, nullptr, false);
     B.a.clear_next = 0;  // the next batch's cursors may already be in use
     B.a.upos = nullptr;
     run_bucket_passes(t, B, s);
     t->timing.end(s);
-    t->batches += 1;
-    t->parity ^= 1;
-    t->flat_valid = false;
   }
-  t->rb = rb_next;
   HIPCHK(hipEventRecord(t->ev_gdone[gi & 1u], s));
   HIPCHK(hipGetLastError());
   return PMDFC_OK;
@@ -1219,14 +1236,11 @@ static bool mixed_join_mode(pmdfc_cceh* t, uint64_t n) {
 static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                      uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
   const uint64_t seq = ++t->seq;
-  if (t->iset_dirty) {  // an earlier batch stopped between its prep and verify passes: start the set empty
-    HIPCHK(hipMemsetAsync(t->iset, 0xFF, (t->imask + 1) * sizeof(uint64_t), s));
-    HIPCHK(hipMemsetAsync(t->icnt, 0, (t->imask + 1) * sizeof(uint32_t), s));
-    HIPCHK(hipMemsetAsync(t->ipos, 0xFF, (t->imask + 1) * sizeof(uint32_t), s));
-    HIPCHK(hipMemsetAsync(t->jbits, 0, kJoinWords * sizeof(uint32_t), s));
-  }
+  // an earlier batch stopped between its prep and verify passes: start the set empty
+  if (int rc = t->iset_dirty ? clear_key_set(t, s) : PMDFC_OK) return rc;
   t->iset_dirty = true;  // (until the verify pass that empties the set is enqueued)
-  if (int rc = batch_geometry(t, false, n, s)) return rc;
+  const BatchPlan b = plan_batch(t, false, n);
+  if (int rc = zero_stale_cursors(t, b, s)) return rc;
   // statuses + early answers + the joining Gets (k_mixed_get), then the
   // inserts' side of the join (k_mixed_join, timed as the pre-pass class);
   // k_part resolves the joining Gets
@@ -1250,7 +1264,7 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   }
   t->last_mixed_n = n;
   PartArgs P{};
-  fill_part_launch(t, P, ops, keys, vin, 1, st, n);
+  fill_part_launch(t, b, P, ops, keys, vin, 1, st, n);
   P.iset = t->iset;
   P.imask = t->imask;
   P.icnt = t->icnt;
@@ -1261,7 +1275,7 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   P.tag = tag;
   P.vout = vout;
   BucketLaunch B{};
-  fill_bucket_launch(t, B, n, st, vout, true);
+  fill_bucket_launch(t, b, B, n, st, vout, true);
   // when k_mixed_get answered every Get, the insert-only apply passes run
   // (upsert batches always take the mixed ones)
   B.a.gate_tag = t->upsert ? 0u : tag;
@@ -1281,10 +1295,7 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   launch_mixed_verify(ops, keys, vin, st, vout, n, t->geo(), t->pairs, t->early, t->elink, t->ctl, t->loss0, t->drops,
                       t->iset, t->icnt, t->ipos, t->islot, t->imask, join ? t->jbits : nullptr, s);
   t->timing.end(s);
-  t->parity ^= 1;
-  t->rb = (t->rb + 1) % kRecBufs;
-  t->clean_sbb = t->sbb;
-  t->flat_valid = false;
+  finish_batch(t, b, kPathGeneral);
   HIPCHK(hipGetLastError());
   t->iset_dirty = false;
   return PMDFC_OK;
@@ -1371,9 +1382,9 @@ static int serve_start(pmdfc_cceh_t* t, uint32_t nwaves, pmdfc_serve_req* req, p
   HIPCHK(hipHostGetDevicePointer(&dq, req, 0));
   HIPCHK(hipHostGetDevicePointer(&dr, resp, 0));
   HIPCHK(hipHostGetDevicePointer(&dc, ctl, 0));
-  if ((rc = batch_geometry(t, false, 64, s, false))) return rc;  // (no records)
+  const BatchPlan b = plan_batch(t, false, 64, false);  // (no records)
   BucketLaunch B{};
-  fill_bucket_launch_direct(t, B, 64, t->srv_st, t->srv_vout);
+  fill_bucket_launch(t, b, B, 64, t->srv_st, t->srv_vout, true);
   ServeArgs V{};
   V.a = B.a;
   V.req = (const pmdfc_serve_req*)dq;
@@ -1387,7 +1398,7 @@ static int serve_start(pmdfc_cceh_t* t, uint32_t nwaves, pmdfc_serve_req* req, p
   V.nwaves = nwaves ? nwaves : 1u;
   launch_serve(V, s);
   HIPCHK(hipGetLastError());
-  t->flat_valid = false;
+  finish_batch(t, b, kPathServe);
   return PMDFC_OK;
 }
 
@@ -1430,15 +1441,14 @@ int pmdfc_cceh_stats(pmdfc_cceh_t* t, pmdfc_cceh_stats_t* out) {
   int rc = read_ctl(t, (hipStream_t)0);
   if (rc) return rc;
   const DevCtl& c = *t->hctl;
-  std::vector<uint64_t> ws((size_t)kWStat << t->p1max);  // (slots of every bucket geometry so far)
-  HIPCHK(hipMemcpy(ws.data(), t->wstat, ws.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> ws;
+  uint32_t max_rounds = 0, max_ld = 0;
+  if ((rc = read_wstat(t, ws, max_ld))) return rc;
   uint64_t sum[kWStat] = {0};
-  uint32_t max_rounds = 0, max_ld = c.max_ld;
   for (size_t i = 0; i < ws.size(); ++i) {
     const int k = (int)(i % kWStat);
     if (k == 6) {
       max_rounds = std::max<uint32_t>(max_rounds, (uint32_t)(ws[i] & 0xFFFF));
-      max_ld = std::max<uint32_t>(max_ld, (uint32_t)((ws[i] >> 16) & 0xFF));
       sum[6] += ws[i] >> 32;
     } else {
       sum[k] += ws[i];
@@ -1499,12 +1509,9 @@ int pmdfc_cceh_dump(pmdfc_cceh_t* t, uint32_t* dir_canon, uint32_t* local_depth,
   HIPCHK(hipDeviceSynchronize());
   int rc = read_ctl(t, (hipStream_t)0);
   if (rc) return rc;
-  uint32_t max_ld = t->hctl->max_ld;
-  {
-    std::vector<uint64_t> ws((size_t)kWStat << t->p1max);
-    HIPCHK(hipMemcpy(ws.data(), t->wstat, ws.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 6; i < ws.size(); i += kWStat) max_ld = std::max<uint32_t>(max_ld, (uint32_t)((ws[i] >> 16) & 0xFF));
-  }
+  std::vector<uint64_t> ws;
+  uint32_t max_ld = 0;
+  if ((rc = read_wstat(t, ws, max_ld))) return rc;
   const uint32_t D = std::max(t->D0, max_ld);  // logical global depth
   const uint32_t Dl = D - t->sbits;
   const uint64_t nlog = 1ULL << Dl;
@@ -1579,7 +1586,7 @@ int pmdfc_cceh_debug_stamps(pmdfc_cceh_t* t, uint64_t* out, uint64_t n, uint32_t
   // the last batch's set, or every set when n holds them all (PMDFC_STAMP_ROT)
   const uint64_t tot = stamp_words(t), all = tot * t->kn.stamp_rot;
   const bool every = t->kn.stamp_rot > 1 && n >= all;
-  const uint64_t* src = every ? t->stamps : (t->stamp_cur ? t->stamp_cur : t->stamps);
+  const uint64_t* src = every || !t->stamp_last ? t->stamps : t->stamp_last;
   HIPCHK(hipMemcpy(out, src, std::min(n, every ? all : tot) * 8, hipMemcpyDeviceToHost));
   if (nbuckets) *nbuckets = 1u << t->p1max;  // (the stamp rows are laid out for p1max)
   return PMDFC_OK;
@@ -2414,22 +2421,13 @@ static int route_batches(pmdfc_router_t* r, pmdfc_cceh_t* t, pmdfc_comm_t* c, ui
     // the caller's arrays with call-global outputs (no pack, no exchange, no
     // unpack; a Get-only batch needs no dedupe).  Inserts go through the
     // engine's partition pipeline as pmdfc_cceh_insert_batches.
-    int e = PMDFC_OK;
-    if (width == 2) {
-      std::vector<uint64_t> rb(nb + 1);
-      for (uint64_t i = 0; i <= nb; ++i) rb[i] = bounds[i] - bounds[0];
-      e = pmdfc_cceh_insert_batches(t, keys + bounds[0], values + bounds[0], st, rb.data(), (uint32_t)nb, S);
-    } else if (width == 3) {
-      std::vector<uint64_t> rb(nb + 1);
-      for (uint64_t i = 0; i <= nb; ++i) rb[i] = bounds[i] - bounds[0];
-      e = pmdfc_cceh_mixed_batches(t, ops + bounds[0], keys + bounds[0], values + bounds[0], vout, st, rb.data(),
-                                   (uint32_t)nb, S);
-    } else {
-      std::vector<uint64_t> rb(nb + 1);
-      for (uint64_t i = 0; i <= nb; ++i) rb[i] = bounds[i] - bounds[0];
-      e = pmdfc_cceh_get_batches(t, keys + bounds[0], vout, st, rb.data(), (uint32_t)nb, S);
-    }
-    return e;
+    const uint64_t o = bounds[0];
+    std::vector<uint64_t> rb(nb + 1);  // the bounds from 0: the outputs are call-global
+    for (uint64_t i = 0; i <= nb; ++i) rb[i] = bounds[i] - o;
+    if (width == 2) return pmdfc_cceh_insert_batches(t, keys + o, values + o, st, rb.data(), (uint32_t)nb, S);
+    if (width == 3)
+      return pmdfc_cceh_mixed_batches(t, ops + o, keys + o, values + o, vout, st, rb.data(), (uint32_t)nb, S);
+    return pmdfc_cceh_get_batches(t, keys + o, vout, st, rb.data(), (uint32_t)nb, S);
   }
   const uint64_t rows = r->rows, cap = r->cfg.cap;
   const bool dd = dedupe && width == 1;

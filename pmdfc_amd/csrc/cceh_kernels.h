@@ -135,9 +135,9 @@ constexpr uint32_t kSplitGroups = PMDFC_SPLIT_GROUPS;  // k_split grid (waves lo
 constexpr uint32_t kRecBufs = PMDFC_RECBUFS;
 
 // The argument structs of bucket.hip's kernels, passed by value.  The engine
-// fills them (cceh_engine.hip fill_part_launch / fill_bucket_launch and the
-// callers that patch a batch kind's fields); the launchers add only what
-// they decide: the kernel, the grid and the gate values.
+// fills them from the batch's BatchPlan (cceh_engine.hip plan_batch, then
+// fill_part_launch / fill_bucket_launch and the callers that patch a batch
+// kind's fields); the launchers add only the kernel, the grid and the gates.
 
 // k_part
 struct PartArgs {

@@ -997,3 +997,92 @@ def test_wide_first_pass_matches_oracle(mixed):
     assert d["depth"] == od["depth"] and np.array_equal(d["local_depth"], od["local_depth"])
     assert np.array_equal(d["keys"], od["keys"]) and np.array_equal(d["values"], od["values"])
     t.close()
+
+
+def _interleave_steps():
+    """The call sequence of test_batch_kinds_interleave_on_one_table: (kind,
+    sizes) with fresh keys uniform_keys(700, ...) consumed in order."""
+    return [("batches", [65536] * 9),  # preload: one full pipeline group and a group of one
+            ("insert", 40000), ("mixed", 30000), ("insert", 40000),
+            ("batches", [40000, 0, 20000, 65536]),
+            ("insert", 5000),  # medium
+            ("insert", 40000),
+            ("mixed", 200),  # small
+            ("mixed", 6000),  # medium
+            ("mixed", 40000),
+            ("batches", [30000, 30000])]
+
+
+def test_batch_kinds_interleave_on_one_table():
+    """Every batch kind on ONE table with no reset in between: pipelined
+    groups (pmdfc_cceh_insert_batches), general insert and mixed batches,
+    medium and small ones.  The table (p1max = 9) is at its bucket resolution
+    from the start, so insert-only batches past 8,192 ops take the coarse
+    partition and mixed ones the fine one: the record-buffer ring, the batch
+    parity and the cursors a batch leaves zeroed for the next one's geometry
+    carry over between the paths.  Every status and value, the final table
+    and the Gets of every stored key equal the serial oracle."""
+    rng = np.random.default_rng(9)
+    t = P.CCEH(depth=10, max_batch=1 << 16, max_segments=8192)
+    o = O.OracleCCEH(10)
+    fresh = 0
+    stored = np.zeros(0, np.uint64)
+    for step, (kind, sizes) in enumerate(_interleave_steps()):
+        n = sum(sizes) if kind == "batches" else sizes
+        k = uniform_keys(700, fresh, n)
+        fresh += n
+        if kind == "mixed":
+            ops = (rng.random(n) < 0.6).astype(np.uint8)
+            g = ops == 0
+            k[g] = np.where(rng.random(int(g.sum())) < 0.8, stored[rng.integers(0, stored.size, int(g.sum()))], k[g])
+            v = k ^ np.uint64(3)
+            out, st = t.Mixed(ops, k, v)
+            oout, ost = o.mixed(ops, k, v)
+            assert np.array_equal(out, oout), step
+            stored = np.concatenate([stored, k[ops == 1]])
+        else:
+            v = k ^ np.uint64(3)
+            if kind == "batches":
+                st = t.InsertBatches(k, v, np.concatenate([[0], np.cumsum(sizes)]).tolist())
+            else:
+                st = t.Insert(k, v)
+            ost = o.insert(k, v)
+            stored = np.concatenate([stored, k])
+        assert np.array_equal(st, ost), step
+    v, st = t.Get(stored)
+    ov, ost = o.get(stored)
+    assert np.array_equal(st, ost) and np.array_equal(v, ov)
+    s = t.stats()
+    assert s["error_flags"] == 0
+    assert s["splits"] > 900
+    d, od = t.dump(), o.dump()
+    assert d["depth"] == od["depth"] and np.array_equal(d["local_depth"], od["local_depth"])
+    assert np.array_equal(d["keys"], od["keys"]) and np.array_equal(d["values"], od["values"])
+    t.close()
+
+
+def test_debug_stamps_follow_the_batch(monkeypatch):
+    """PMDFC_STAMPS=1 (a create knob): the stamps pmdfc_cceh_debug_stamps
+    returns are those of the LAST batch, through the one-batch path and through
+    the pipelined one.  A 40,000-op batch has five k_part blocks, each stamping
+    its start (word 0) and end (word 3); every first-pass wave stamps phase 0
+    of its bucket's row; the counter is a wall clock, so a later batch's
+    stamps are greater."""
+    monkeypatch.setenv("PMDFC_STAMPS", "1")
+    t = P.CCEH(depth=10, max_batch=1 << 16, max_segments=8192)
+    keys = uniform_keys(701, 0, 100000)
+    vals = keys ^ np.uint64(3)
+    assert np.all(t.Insert(keys[:40000], vals[:40000]) == P.ST_INSERTED)
+    bk, pt, sp = t.debug_stamps(1 << 16)
+    assert bk.shape == (512, 16) and pt.shape == (8, 8)
+    assert np.all(pt[:5, 0] > 0) and np.all(pt[:5, 3] >= pt[:5, 0])
+    assert np.all(pt[5:] == 0)  # (zeroed at create, never written by a five-block batch)
+    assert np.all(bk[:, 0] > 0)
+    bk, pt = bk.copy(), pt.copy()
+    # the pipelined path: its last batch (40,000 ops again) owns the set read
+    assert np.all(t.InsertBatches(keys[40000:], vals[40000:], [0, 20000, 60000]) == P.ST_INSERTED)
+    bk2, pt2, sp2 = t.debug_stamps(1 << 16)
+    assert np.all(pt2[:5, 0] > pt[:5, 3])
+    assert np.all(bk2[:, 0] > bk[:, 0])
+    assert t.stats()["error_flags"] == 0
+    t.close()
