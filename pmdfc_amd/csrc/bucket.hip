@@ -33,6 +33,12 @@
 // Small batches skip the pipeline: k_mixed_tiny (<= 64 ops), k_mixed_small
 // (<= 256) and k_part + k_medium (<= 8192) run the final pass's ordered runs
 // directly.
+//
+// bucket_body is the outline of a bucket pass over named phases ("the phases
+// of a bucket pass": chunk loaders, entry lookup, the two orderings into
+// runs, apply_runs, the claim write-outs, parking, grow_and_split); what the
+// first passes share with the lean apply_fast exists once ("what every first
+// pass of a batch does"); the stamp slots are named under "debug stamps".
 #include <algorithm>
 #include <cstdlib>
 #include <cstddef>
@@ -64,6 +70,35 @@ __device__ __forceinline__ uint32_t sk_seg(uint64_t k) { return (uint32_t)(k >> 
 __device__ __forceinline__ uint32_t sk_op(uint64_t k) { return (uint32_t)(k >> 17) & kOpMask; }
 __device__ __forceinline__ uint32_t sk_item(uint64_t k) { return (uint32_t)(k >> 8) & 511u; }
 __device__ __forceinline__ uint32_t sk_home(uint64_t k) { return (uint32_t)k & 0xFFu; }
+
+// ------------------------------------------------------------ debug stamps
+//
+// PMDFC_STAMPS=1: a wave stores wall_clock64() into its row of the batch's
+// stamp set as it passes each phase (pmdfc_cceh_read_stamps; phase_stamps.py
+// turns the rows into phase lengths).  row: null when stamps are off; writer:
+// the one lane that stores.
+__device__ __forceinline__ void stamp(uint64_t* row, uint32_t slot, bool writer) {
+  if (row && writer) row[slot] = wall_clock64();
+}
+// k_part, 8 slots per block: start, tile counted, runs reserved, end
+enum : uint32_t { kPsStart, kPsCounted, kPsReserved, kPsEnd };
+// k_split, 8 slots per split: descriptors built, cluster starts known, replay
+// done, parent pairs reloaded, stores issued, start, the replay taken (a
+// value: 1 clusters, 2 generic), wrap unit replayed
+enum : uint32_t { kSsHashed, kSsClusters, kSsReplayed, kSsReloaded, kSsStored, kSsStart, kSsPath, kSsWrapUnit };
+// Bucket passes, 16 slots per directory bucket.  First pass: start, chunk
+// loaded, round 0 ordered into runs (fast_claim: 0, no sort), its claims
+// written, its ops binned by segment, in batch order, its runs applied
+// (fast_claim: decisions final), end.  Final pass, 8-13: start, loaded, round
+// 0 ordered, written, split, end.  14, 15: a first-pass run's claim loop and
+// end (last writer).  fast_claim keeps its own three in 10-12, which a final
+// pass of the same bucket overwrites: dependency masks built, rounds |
+// dependent inserts << 16 (a value), dependent inserts resolved.
+enum : uint32_t {
+  kBsStart, kBsLoaded, kBsOrdered, kBsWritten, kBsBinned, kBsBatchOrder, kBsRunsDone, kBsEnd,
+  kBsFinStart, kBsFinLoaded, kBsFinOrdered, kBsFinWritten, kBsFinSplit, kBsFinEnd, kBsRunClaimed, kBsRunEnd,
+  kBsFcMasks = 10, kBsFcRounds = 11, kBsFcResolved = 12,
+};
 
 // --------------------------------------------------------------- partition
 
@@ -110,16 +145,14 @@ __device__ __forceinline__ uint8_t join_resolve(const PartArgs& a, uint64_t p, u
   return s;
 }
 
-#define PART_STAMP(ph) \
-  if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 8 + (ph)] = wall_clock64()
-
 __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
   // 64 KB of LDS: a block fits beside a CU's share of the apply pass, which
   // it overlaps in pipelined insert batches (the overflow slot of a run that
   // does not fit its sub-region, rare, goes through global memory: a.povf)
   __shared__ uint32_t s_cnt[1u << kMaxPartBits];  // ops of the tile per bucket
   __shared__ uint32_t s_reg[1u << kMaxPartBits];  // region slot of the bucket's run
-  PART_STAMP(0);
+  uint64_t* const srow = a.stamps ? a.stamps + (size_t)blockIdx.x * 8 : nullptr;
+  stamp(srow, kPsStart, threadIdx.x == 0);
   const uint32_t nb = 1u << a.pbits;
   for (uint32_t i = threadIdx.x; i < nb; i += kPartThreads) s_cnt[i] = 0;
   __syncthreads();
@@ -174,7 +207,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
     }
   }
   __syncthreads();
-  PART_STAMP(1);
+  stamp(srow, kPsCounted, threadIdx.x == 0);
   if (a.touched) {  // one block (medium batch): the partition buckets that received ops
     __shared__ uint32_t s_nt;
     if (threadIdx.x == 0) s_nt = 0;
@@ -214,7 +247,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
     }
   }
   __syncthreads();
-  PART_STAMP(2);
+  stamp(srow, kPsReserved, threadIdx.x == 0);
 #pragma unroll
   for (int k = 0; k < kPartPer; ++k) {
     const uint32_t b = bk[k];
@@ -233,7 +266,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part(PartArgs a) {
   }
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
-  PART_STAMP(3);
+  stamp(srow, kPsEnd, threadIdx.x == 0);
 }
 
 // ------------------------------------------------------------------ helpers
@@ -243,9 +276,6 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
-
-__device__ __forceinline__ uint64_t umin64(uint64_t x, uint64_t y) { return x < y ? x : y; }
-__device__ __forceinline__ uint64_t umax64(uint64_t x, uint64_t y) { return x < y ? y : x; }
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
   const int lo = __shfl_xor((int)(uint32_t)v, m);
@@ -265,57 +295,18 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t* total) 
   return incl - v;
 }
 
-// Ascending bitonic sort, by one wave, of s[0..nvalid) padded with ~0 to n
-// (a power of two <= kCW); s[0..n) holds the result.  Element e lives in
-// lane e/8, register e%8: partner distances j < 8 stay in the lane, larger
-// ones are cross-lane shuffles (j/8 <= 32).  Elements >= n only meet each
-// other, so every lane runs the same network.
-__device__ __forceinline__ void wave_sort8(uint64_t* s, uint32_t n, uint32_t nvalid) {
+// Ascending bitonic sort by one wave of keys held in registers: position
+// KP*lane + q in v[q], n a power of two <= 64*KP, positions >= n hold ~0
+// (they only meet each other, so every lane runs the same network).  Partner
+// distances j < KP stay in the lane, larger ones are cross-lane shuffles
+// (j/KP <= 32).
+__device__ __forceinline__ uint32_t shfl_xor_key(uint32_t v, int m) { return (uint32_t)__shfl_xor((int)v, m); }
+__device__ __forceinline__ uint64_t shfl_xor_key(uint64_t v, int m) { return shfl_xor64(v, m); }
+template <class T, int KP>
+__device__ __forceinline__ void wave_sort_regs(T (&v)[KP], uint32_t n) {
   const uint32_t lane = __lane_id() & 63u;
-  uint64_t v[kPer];
-#pragma unroll
-  for (int q = 0; q < kPer; ++q) v[q] = (kPer * lane + q < nvalid) ? s[kPer * lane + q] : ~0ULL;
-  for (uint32_t k = 2; k <= n; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      if (j >= (uint32_t)kPer) {
-        const int m = (int)(j / kPer);
-#pragma unroll
-        for (int q = 0; q < kPer; ++q) {
-          const uint32_t e = kPer * lane + q;
-          const uint64_t pv = shfl_xor64(v[q], m);
-          const bool up = (e & k) == 0, lower = (e & j) == 0;
-          v[q] = (lower == up) ? umin64(v[q], pv) : umax64(v[q], pv);
-        }
-      } else {
-        // in-lane partners: dispatch on j so every register index is static
-        // (a runtime v[q + j] would put v[] in scratch memory)
-#pragma unroll
-        for (int jj = kPer / 2; jj >= 1; jj >>= 1) {
-          if ((int)j != jj) continue;
-#pragma unroll
-          for (int q = 0; q < kPer; ++q) {
-            if (q & jj) continue;
-            const uint32_t e = kPer * lane + q;
-            const bool up = (e & k) == 0;
-            const uint64_t x = v[q], y = v[q + jj];
-            v[q] = up ? umin64(x, y) : umax64(x, y);
-            v[q + jj] = up ? umax64(x, y) : umin64(x, y);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kPer; ++q)
-    if (kPer * lane + q < n) s[kPer * lane + q] = v[q];
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Ascending bitonic sort of 32-bit keys held in registers: position
-// KP*lane + q in v[q], n a power of two <= 64*KP, positions >= n hold ~0.
-template <int KP>
-__device__ __forceinline__ void wave_sort32(uint32_t (&v)[KP], uint32_t n) {
-  const uint32_t lane = __lane_id() & 63u;
+  const auto lo = [](T x, T y) { return x < y ? x : y; };
+  const auto hi = [](T x, T y) { return x < y ? y : x; };
   for (uint32_t k = 2; k <= n; k <<= 1) {
     for (uint32_t j = k >> 1; j > 0; j >>= 1) {
       if (j >= (uint32_t)KP) {
@@ -323,11 +314,13 @@ __device__ __forceinline__ void wave_sort32(uint32_t (&v)[KP], uint32_t n) {
 #pragma unroll
         for (int q = 0; q < KP; ++q) {
           const uint32_t e = KP * lane + q;
-          const uint32_t pv = (uint32_t)__shfl_xor((int)v[q], m);
+          const T pv = shfl_xor_key(v[q], m);
           const bool up = (e & k) == 0, lower = (e & j) == 0;
-          v[q] = (lower == up) ? min(v[q], pv) : max(v[q], pv);
+          v[q] = (lower == up) ? lo(v[q], pv) : hi(v[q], pv);
         }
       } else {
+        // in-lane partners: dispatch on j so every register index is static
+        // (a runtime v[q + j] would put v[] in scratch memory)
 #pragma unroll
         for (int jj = KP / 2; jj >= 1; jj >>= 1) {
           if ((int)j != jj) continue;
@@ -336,14 +329,31 @@ __device__ __forceinline__ void wave_sort32(uint32_t (&v)[KP], uint32_t n) {
             if (q & jj) continue;
             const uint32_t e = KP * lane + q;
             const bool up = (e & k) == 0;
-            const uint32_t x = v[q], y = v[q + jj];
-            v[q] = up ? min(x, y) : max(x, y);
-            v[q + jj] = up ? max(x, y) : min(x, y);
+            const T x = v[q], y = v[q + jj];
+            v[q] = up ? lo(x, y) : hi(x, y);
+            v[q + jj] = up ? hi(x, y) : lo(x, y);
           }
         }
       }
     }
   }
+}
+template <int KP>
+__device__ __forceinline__ void wave_sort32(uint32_t (&v)[KP], uint32_t n) {
+  wave_sort_regs<uint32_t, KP>(v, n);
+}
+// s[0..nvalid) in LDS, padded with ~0 to n (a power of two <= kCW), sorted in
+// place: s[0..n) holds the result
+__device__ __forceinline__ void wave_sort8(uint64_t* s, uint32_t n, uint32_t nvalid) {
+  const uint32_t lane = __lane_id() & 63u;
+  uint64_t v[kPer];
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) v[q] = (kPer * lane + q < nvalid) ? s[kPer * lane + q] : ~0ULL;
+  wave_sort_regs<uint64_t, kPer>(v, n);
+#pragma unroll
+  for (int q = 0; q < kPer; ++q)
+    if (kPer * lane + q < n) s[kPer * lane + q] = v[q];
+  __builtin_amdgcn_wave_barrier();
 }
 
 // Positions < n of a 32-bit key array in LDS, sorted in place by one wave
@@ -479,14 +489,12 @@ __device__ __noinline__ uint32_t split_slow(const uint16_t* s_inf, uint16_t* s_d
 // 0's.  Returns dropped entries (the team's total, on every wave); *bad_out
 // is set if an internal assumption failed (reported as a sticky device
 // error).  NW = 4 needs every wave of the workgroup (barriers).
-#define SP_STAMP(k) \
-  if (stamp && lane == 0 && v == 0) stamp[k] = wall_clock64()
 // drops != null (mixed batches): each dropped entry is logged as {key, trig},
 // trig = the batch position of the insert whose full window split `seg`.
 template <int NW>
 __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, uint32_t* __restrict__ occ,
                                                uint8_t* __restrict__ ldep, uint32_t seg, uint32_t c1, uint32_t L,
-                                               uint32_t* scr, bool* bad_out, uint64_t* stamp, ulonglong2* drops,
+                                               uint32_t* scr, bool* bad_out, uint64_t* srow, ulonglong2* drops,
                                                uint32_t* drop_n, uint32_t trig, uint32_t v) {
   static_assert(NW == 1 || NW == 4, "team of 1 or 4 waves");
   constexpr int G = 16 / NW;  // slot groups per wave
@@ -558,7 +566,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
   }
   if (NW > 1 && __ballot(far) && lane == 0) atomicOr(&s_tm[0], 1u);
   team_barrier();
-  SP_STAMP(0);
+  stamp(srow, kSsHashed, lane == 0 && v == 0);
   uint32_t loss = 0;
   if (v == 0) {
     bool bad = far || (NW > 1 && (s_tm[0] & 1u));
@@ -576,7 +584,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
     const int tl = nzw ? 63 - __builtin_clzll(nzw) : 0;
     const uint32_t tail = (uint32_t)__shfl((int)(tl * 32 + (stw ? 31 - __builtin_clz(stw) : 0)), tl);
     const uint32_t head_end = cyclic ? occ_end(s_occ, 0) : 0u;
-    SP_STAMP(1);
+    stamp(srow, kSsClusters, lane == 0);
     bool wide = false;  // a unit outgrew the 128-bit window
     if (!all_full) {
       if (cyclic && wl == 0) {
@@ -593,7 +601,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
         unit_range(s_inf, s_occ, s_ch1, s_dst, lo, hi, c, tail, tail, kSlots, &loss, &wide);
         unit_flush(s_cb, lo, hi, c, tail);
       }
-      if (stamp && lane == 0) stamp[7] = wall_clock64();
+      stamp(srow, kSsWrapUnit, lane == 0);
       // The other clusters: a sweep over positions, each 32-slot word by its
       // own lane.  Outside the wrap unit an entry at parent slot s with window
       // start w lands at some x in [w, s] of its child (the slots [w, s) hold at
@@ -687,7 +695,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
       __builtin_amdgcn_wave_barrier();
     }
     const bool fast = !all_full && __ballot(wide) == 0;
-    if (stamp && lane == 0) stamp[6] = fast ? 1 : 2;
+    if (srow && lane == 0) srow[kSsPath] = fast ? 1 : 2;
     if (!fast) {
       // a full parent or a unit wider than 128 slots: the generic replay
       // rewrites every placement and both child bitmaps
@@ -702,7 +710,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
     }
     if (NW == 1) *bad_out = bad;
   }
-  SP_STAMP(2);
+  stamp(srow, kSsReplayed, lane == 0 && v == 0);
   // every child slot is written exactly once: an entry or INVALID.  Child 0
   // is the parent's storage, so every parent pair is reloaded (L2-hot) into
   // registers before the first store (of any wave of the team); the stores
@@ -724,7 +732,7 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
     loss = s_tm[1];
     *bad_out = (s_tm[0] & 2u) != 0;
   }
-  SP_STAMP(3);
+  stamp(srow, kSsReloaded, lane == 0 && v == 0);
 #pragma unroll
   for (int j = 0; j < G; ++j) {
     const uint32_t slot = (uint32_t)(g0 + j) * 64u + lane;
@@ -754,17 +762,17 @@ __device__ __forceinline__ uint32_t split_team(ulonglong2* __restrict__ pairs, u
       ldep[c1] = (uint8_t)(L + 1);
     }
   }
-  SP_STAMP(4);  // the stores may still be in flight (callers wait when they re-read)
+  stamp(srow, kSsStored, lane == 0 && v == 0);  // the stores may still be in flight (callers wait when they re-read)
   if constexpr (NW > 1) team_barrier();  // (the scratch is reused by the team's next split)
   return loss;
 }
 
 __device__ __forceinline__ uint32_t wave_split(ulonglong2* __restrict__ pairs, uint32_t* __restrict__ occ,
                                                uint8_t* __restrict__ ldep, uint32_t seg, uint32_t c1, uint32_t L,
-                                               uint32_t* scr, bool* bad_out, uint64_t* stamp,
+                                               uint32_t* scr, bool* bad_out, uint64_t* srow,
                                                ulonglong2* drops = nullptr, uint32_t* drop_n = nullptr,
                                                uint32_t trig = 0) {
-  return split_team<1>(pairs, occ, ldep, seg, c1, L, scr, bad_out, stamp, drops, drop_n, trig, 0u);
+  return split_team<1>(pairs, occ, ldep, seg, c1, L, scr, bad_out, srow, drops, drop_n, trig, 0u);
 }
 
 // ------------------------------------------------------------------ bucket
@@ -774,10 +782,10 @@ constexpr uint64_t kServeWatchdog = 100000000ull;  // wall_clock64 ticks (100 MH
 constexpr uint64_t kServeIdle = 100000ull;         // ~1 ms without ops: raise ctl->idle (callers on a CPU-
                                                    // quota'd host pause for longer than 100 us at times)
 
-// 0 start, 1 collected, 2 round-0 sorted, 3 round-0 applied, 7 end (first
-// k_apply pass); 8..13 the same for the final pass (12: round-0 splits done)
-#define BK_STAMP(ph) \
-  if (a.stamps && lane == 0) a.stamps[(size_t)w * 16 + (ph)] = wall_clock64()
+// a bucket wave's stamp row (debug stamps above), or null
+__device__ __forceinline__ uint64_t* bucket_stamp_row(const BucketArgs& a, uint32_t w) {
+  return a.stamps ? a.stamps + (size_t)w * 16 : nullptr;
+}
 
 constexpr uint32_t kBmWords = kBmLanes * 33;
 constexpr uint32_t kUnionWords = kBmWords > kSplitScratch ? kBmWords : kSplitScratch;
@@ -1026,6 +1034,39 @@ __device__ __noinline__ bool window_all_same_reg(const ulonglong2* sp, const uin
   return true;
 }
 
+constexpr uint32_t kBigBucket = 0xFFFFFFFFu;  // wl_n of a bucket with more ops than a chunk: the final pass walks its records
+constexpr uint32_t kLdsDir = 128;  // k_apply: sub-directories up to this size are read into LDS
+
+// LDS of one bucket wave; the apply pass (no splits) carries no split state,
+// which keeps its footprint, and so its occupancy, lower.
+template <bool FINAL, bool REG>
+struct BucketLds {
+  uint32_t u[FINAL ? kUnionWords : kBmWords];  // run phase: per-lane bitmaps; split phase: scratch
+  uint64_t sk[kCW];       // sort keys of the pending ops
+  ulonglong2 kv[REG ? 1 : kCW];   // {key, value} of each chunk slot (REG: in registers)
+  uint64_t key[REG ? kCW : 1];    // REG: the key of each chunk slot
+  uint32_t op[REG ? 1 : kCW];     // rop word of each chunk slot (REG: in registers)
+  uint16_t pos[kCW];      // insert-only: slot claimed this round, 0xFFFF none
+  uint16_t runq[kCW + 1];
+  uint8_t L[kCW];         // local depth of the op's segment | Get << 7
+  uint8_t pend[kCW];
+  uint64_t split[FINAL ? kSplitCap : 1];
+  uint32_t dir[FINAL ? 1 : kLdsDir];           // apply pass: the bucket's sub-directory
+  uint32_t nsplit, nreq, need;
+};
+// the REG collect path stages kCW {key, value} pairs across u and sk
+using BucketLdsReg = BucketLds<false, true>;
+static_assert(offsetof(BucketLdsReg, sk) == sizeof(uint32_t) * kBmWords &&
+                  sizeof(uint32_t) * kBmWords + sizeof(uint64_t) * kCW >= sizeof(ulonglong2) * kCW,
+              "REG collect staging spans u and sk");
+
+// The per-wave counters of a bucket pass, added to the bucket's stat slots by
+// publish_stats (lines and waited are per lane, the others wave-uniform).
+struct WaveStat {
+  uint32_t lines = 0, waited = 0, splits = 0, loss = 0, runs = 0, rounds = 0;
+  uint32_t max_rounds = 0, max_ld = 0, grow = 0, bad = 0;
+};
+
 struct RunCtx {  // what one run needs (passed by value: no kernarg copies)
   ulonglong2* pairs;
   uint32_t* occ;
@@ -1039,6 +1080,8 @@ struct RunCtx {  // what one run needs (passed by value: no kernarg copies)
   uint32_t sbits, p1, db;  // geometry of the request's sub-index
   uint32_t upsert;  // last-writer-wins Insert
   const uint16_t* upos;  // upsert, first apply pass: pre-batch key slots by op index, else null
+  ulonglong2* wl_kv;  // this bucket's wait list (k_apply parks the rest of a blocked run there)
+  uint32_t* wl_op;
 };
 
 // Upsert (last-writer-wins, CCEH_hybrid.cpp:153's overwrite clause enabled):
@@ -1065,233 +1108,248 @@ __device__ __forceinline__ int upsert_find(const ulonglong2* sp, const uint32_t*
   return -1;
 }
 
+// a segment's occupancy bitmap, loaded as 8 x uint4, into its 33-word LDS row
+__device__ __forceinline__ void put_bitmap_row(uint32_t* row, const uint4 (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    row[4 * j] = v[j].x;
+    row[4 * j + 1] = v[j].y;
+    row[4 * j + 2] = v[j].z;
+    row[4 * j + 3] = v[j].w;
+  }
+}
+
+// the key of chunk slot i (REG: the insert-only apply passes keep the pairs in
+// registers; the runs see the keys only)
+template <bool REG, class Lds>
+__device__ __forceinline__ uint64_t chunk_key(const Lds& S, uint32_t i) {
+  if constexpr (REG) return S.key[i];
+  else return S.kv[i].x;
+}
+
+// Upsert: the slot that already belongs to `key` as op q of the run [q0, ..)
+// comes to it, or -1 -- a claim of this run not yet stored (insert-only
+// batches store after the run loop; the earlier claim is dropped, this op
+// writes the slot; S.pos keeps the slot each op of the round took in mixed
+// batches too), else the key's slot in memory (first pass: the pre-batch
+// probe a.upos, no split of this batch having run yet).
+template <bool REG, class Lds>
+__device__ __forceinline__ int upsert_slot(const RunCtx& a, Lds& S, const ulonglong2* sp, const uint32_t* bm,
+                                           uint32_t q0, uint32_t q, uint64_t key, uint32_t op, uint32_t wi0) {
+  int upos = -1;
+  for (uint32_t qq = q0; qq < q; ++qq) {
+    const uint32_t i2 = sk_item(S.sk[qq]);
+    if (S.pos[i2] != 0xFFFFu && chunk_key<REG>(S, i2) == key) {
+      upos = S.pos[i2];
+      S.pos[i2] = 0xFFFF;
+    }
+  }
+  if (upos >= 0) return upos;
+  if (!a.upos) return upsert_find(sp, bm, wi0, key);
+  const uint32_t u = a.upos[op];
+  return u == 0xFFFFu ? -1 : (int)u;
+}
+
+// The apply passes' common case: a wave-uniform loop (exit by ballot) with a
+// branch-free body that only claims slots (S.pos, the bitmap row bm).  It
+// stops a lane at its first full window -- or, in a mixed batch, at its first
+// Get -- where apply_run's general loop takes over (go = false, upsert
+// batches: from the start, since an insert first looks for its key).
+// Returns the first op it did not take; adds the lines its claims probed.
+template <bool MIXED, class Lds>
+__device__ __forceinline__ uint32_t claim_loop(Lds& S, uint32_t* bm, uint32_t q0, uint32_t q1, bool go,
+                                               uint32_t& lines) {
+  uint32_t qs = q0;
+  uint64_t skn = S.sk[q0];
+  for (uint32_t q = q0;; ++q) {
+    const bool act = go && q < q1;
+    if (__ballot(act) == 0) break;
+    if (act) {
+      const uint64_t skq = skn;
+      skn = S.sk[min(q + 1u, (uint32_t)kCW - 1u)];  // read ahead
+      const uint32_t wi0 = sk_home(skq) * 4u;
+      const uint32_t wi = wi0 >> 5, wn = (wi + 1u) & 31u;
+      const uint32_t lo = bm[wi], hi = bm[wn];
+      const uint32_t fr = ~__builtin_amdgcn_alignbit(hi, lo, wi0 & 31u);
+      bool ok = fr != 0;
+      if constexpr (MIXED) ok = ok && !(S.L[sk_item(skq)] & 0x80u);  // a Get: the general loop
+      const uint32_t t = (uint32_t)__builtin_ctz(fr | (ok ? 0u : 1u));
+      const uint32_t b = ok ? 1u << ((wi0 + t) & 31u) : 0u;
+      const bool in_lo = (wi0 & 31u) + t < 32u;
+      bm[wi] = lo | (in_lo ? b : 0u);  // both words written: no divergent branch
+      bm[wn] = hi | (in_lo ? 0u : b);
+      if (ok) S.pos[sk_item(skq)] = (uint16_t)((wi0 + t) & (kSlots - 1));
+      lines += ok ? (t >> 2) + 1 : 0u;
+      qs = ok ? q + 1 : qs;
+      go = ok;
+    }
+  }
+  return qs;
+}
+
 // One segment run (ops q0..q1 of the sorted chunk, one segment), by one lane,
 // against an LDS copy of the segment's occupancy bitmap.  A full window stops
 // the run: k_apply requests a split (granted at the end of the pass, done by
 // k_split) and parks the rest of the run; the final pass splits inline.
 template <bool FINAL, bool MIXED>
-__device__ __forceinline__ uint2 apply_run(RunCtx a, const uint64_t* s_sk, uint32_t q0, uint32_t q1,
-                                        const uint8_t* s_L, const ulonglong2* s_kv, const uint64_t* s_key,
-                                        const uint32_t* s_op,
-                                        uint16_t* s_pos, uint8_t* s_pend, uint64_t* s_split,
-                                        uint32_t* s_nsplit, uint32_t* s_nreq, uint32_t* s_need, uint32_t* bm,
-                                        ulonglong2* wl_kv, uint32_t* wl_op, bool pre) {
-  // REG: the insert-only apply passes keep each op's pair in its owner lane's
-  // registers; the run sees the keys (s_key) only
+__device__ __forceinline__ uint2 apply_run(RunCtx a, BucketLds<FINAL, !FINAL && !MIXED>& S, uint32_t q0, uint32_t q1,
+                                           bool pre) {
   constexpr bool REG = !FINAL && !MIXED;
-  const auto key_of = [&](uint32_t i) -> uint64_t {
-    if constexpr (REG) return s_key[i];
-    else return s_kv[i].x;
-  };
   const uint32_t lbase = a.sbits + a.p1;
+  uint32_t* const bm = S.u + ((__lane_id() & 63u) % kBmLanes) * 33u;  // this lane's bitmap row
   uint32_t lines = 0, waited = 0;
-    const uint64_t sk0 = s_sk[q0];
-    const uint32_t seg = sk_seg(sk0);
-    const uint32_t L = s_L[sk_item(sk0)] & 31u;
-    if (!pre) {  // (the apply pass prefetches the bitmaps of its first kBmLanes runs)
-      const uint32_t* og = a.occ + (size_t)seg * 32u;
-      uint4 bv[8];
+  const uint64_t sk0 = S.sk[q0];
+  const uint32_t seg = sk_seg(sk0);
+  const uint32_t L = S.L[sk_item(sk0)] & 31u;
+  if (!pre) {  // (the apply pass prefetches the bitmaps of its first kBmLanes runs)
+    const uint32_t* og = a.occ + (size_t)seg * 32u;
+    uint4 bv[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) bv[j] = ld_u4_l2(og + 4 * j);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bm[4 * j] = bv[j].x;
-        bm[4 * j + 1] = bv[j].y;
-        bm[4 * j + 2] = bv[j].z;
-        bm[4 * j + 3] = bv[j].w;
+    for (int j = 0; j < 8; ++j) bv[j] = ld_u4_l2(og + 4 * j);
+    put_bitmap_row(bm, bv);
+  }
+  ulonglong2* sp = a.pairs + (size_t)seg * kSlots;
+  bool dirty = false;
+  uint32_t qs = q0;
+  if constexpr (!FINAL) {
+    qs = claim_loop<MIXED>(S, bm, q0, q1, !a.upsert, lines);
+    dirty = qs > q0;
+    if constexpr (MIXED) {
+      // the general loop goes on (a Get, or a full window it inspects): it
+      // reads the segment, so the claims made so far are stored first
+      if (qs > q0 && qs < q1) {
+        for (uint32_t qq = q0; qq < qs; ++qq) {
+          const uint64_t sk = S.sk[qq];
+          const uint32_t i2 = sk_item(sk);
+          sp[S.pos[i2]] = S.kv[i2];
+          a.st[sk_op(sk)] = 2;  // PMDFC_ST_INSERTED
+          S.pos[i2] = 0xFFFF;
+        }
       }
     }
-    ulonglong2* sp = a.pairs + (size_t)seg * kSlots;
-    bool dirty = false;
-    uint32_t qs = q0;
-    if constexpr (!FINAL) {
-      // the apply passes' common case: a wave-uniform loop (exit by ballot)
-      // with a branch-free body that only claims slots; it stops a lane at
-      // its first full window -- or, in a mixed batch, at its first Get --
-      // where the general loop below takes over (upsert batches take the
-      // general loop: an insert first looks for its key)
-      bool go = !a.upsert;
-      uint64_t skn = s_sk[q0];
-      for (uint32_t q = q0;; ++q) {
-        const bool act = go && q < q1;
-        if (__ballot(act) == 0) break;
-        if (act) {
-          const uint64_t skq = skn;
-          skn = s_sk[min(q + 1u, (uint32_t)kCW - 1u)];  // read ahead
-          const uint32_t wi0 = sk_home(skq) * 4u;
-          const uint32_t wi = wi0 >> 5, wn = (wi + 1u) & 31u;
-          const uint32_t lo = bm[wi], hi = bm[wn];
-          const uint32_t fr = ~__builtin_amdgcn_alignbit(hi, lo, wi0 & 31u);
-          bool ok = fr != 0;
-          if constexpr (MIXED) ok = ok && !(s_L[sk_item(skq)] & 0x80u);  // a Get: the general loop
-          const uint32_t t = (uint32_t)__builtin_ctz(fr | (ok ? 0u : 1u));
-          const uint32_t b = ok ? 1u << ((wi0 + t) & 31u) : 0u;
-          const bool in_lo = (wi0 & 31u) + t < 32u;
-          bm[wi] = lo | (in_lo ? b : 0u);  // both words written: no divergent branch
-          bm[wn] = hi | (in_lo ? 0u : b);
-          if (ok) s_pos[sk_item(skq)] = (uint16_t)((wi0 + t) & (kSlots - 1));
-          lines += ok ? (t >> 2) + 1 : 0u;
-          qs = ok ? q + 1 : qs;
-          go = ok;
-        }
+    stamp(a.stamp, kBsRunClaimed, (__lane_id() & 63u) == 0);
+  }
+  uint64_t nxt = qs < q1 ? S.sk[qs] : 0ULL;
+  uint64_t memo_k = kInvalid, memo_v = 0;  // mixed: last Get probe of this run
+  uint8_t memo_s = 0;
+  for (uint32_t q = qs; q < q1; ++q) {
+    const uint64_t skq = nxt;
+    if (q + 1 < q1) nxt = S.sk[q + 1];  // prefetch the next op's key
+    const uint32_t i = sk_item(skq);
+    const uint32_t op = sk_op(skq);
+    if (MIXED && (S.L[i] & 0x80u)) {
+      // a Get sees the run's earlier inserts only through its own key
+      // (others just fill empty slots past or instead of the probe's end),
+      // so repeated Gets of one key reuse the last probe until that key
+      // is inserted (hot keys of skewed batches)
+      const uint64_t key = S.kv[i].x;
+      if (key != memo_k) {
+        memo_v = 0;
+        memo_s = lane_probe(sp, key, hash64(key), &memo_v);
+        memo_k = key;
       }
-      dirty = qs > q0;
-      if constexpr (MIXED) {
-        // the general loop goes on (a Get, or a full window it inspects): it
-        // reads the segment, so the claims made so far are stored first
-        if (qs > q0 && qs < q1) {
-          for (uint32_t qq = q0; qq < qs; ++qq) {
-            const uint64_t sk = s_sk[qq];
-            const uint32_t i2 = sk_item(sk);
-            sp[s_pos[i2]] = s_kv[i2];
-            a.st[sk_op(sk)] = 2;  // PMDFC_ST_INSERTED
-            s_pos[i2] = 0xFFFF;
-          }
-        }
-      }
-      if (a.stamp && (__lane_id() & 63u) == 0) a.stamp[14] = wall_clock64();
+      a.vout[op] = memo_v;
+      a.st[op] = memo_s;
+      S.pend[i] = 0;
+      continue;
     }
-    uint64_t nxt = qs < q1 ? s_sk[qs] : 0ULL;
-    uint64_t memo_k = kInvalid, memo_v = 0;  // mixed: last Get probe of this run
-    uint8_t memo_s = 0;
-    for (uint32_t q = qs; q < q1; ++q) {
-      const uint64_t skq = nxt;
-      if (q + 1 < q1) nxt = s_sk[q + 1];  // prefetch the next op's key
-      const uint32_t i = sk_item(skq);
-      const uint32_t op = sk_op(skq);
-      if (MIXED && (s_L[i] & 0x80u)) {
-        // a Get sees the run's earlier inserts only through its own key
-        // (others just fill empty slots past or instead of the probe's end),
-        // so repeated Gets of one key reuse the last probe until that key
-        // is inserted (hot keys of skewed batches)
-        const uint64_t key = s_kv[i].x;
-        if (key != memo_k) {
-          memo_v = 0;
-          memo_s = lane_probe(sp, key, hash64(key), &memo_v);
-          memo_k = key;
-        }
-        a.vout[op] = memo_v;
-        a.st[op] = memo_s;
-        s_pend[i] = 0;
-        continue;
-      }
-      const uint32_t wi0 = sk_home(skq) * 4u;
-      const uint32_t wi = wi0 >> 5;
-      if (a.upsert) {
-        // last-writer-wins: the key's own slot takes the pair if it has one --
-        // a claim of this run not yet stored (insert-only batches store after
-        // the run loop; the earlier claim is dropped, this op writes the slot),
-        // else the window in memory
-        // (s_pos: the slot each op of the round took, kept by mixed batches
-        // too, so a claim of the key earlier in this run is found here)
-        const uint64_t key = key_of(i);
-        int upos = -1;
-        for (uint32_t qq = q0; qq < q; ++qq) {
-          const uint32_t i2 = sk_item(s_sk[qq]);
-          if (s_pos[i2] != 0xFFFFu && key_of(i2) == key) {
-            upos = s_pos[i2];
-            s_pos[i2] = 0xFFFF;
-          }
-        }
-        if (upos < 0) {
-          if (a.upos) {  // first pass: the pre-batch probe (no split of this batch yet)
-            const uint32_t u = a.upos[op];
-            upos = u == 0xFFFFu ? -1 : (int)u;
-          } else {
-            upos = upsert_find(sp, bm, wi0, key);
-          }
-        }
-        if (upos >= 0) {
-          s_pos[i] = (uint16_t)upos;
-          if (MIXED) {
-            if (key == memo_k) memo_k = kInvalid;
-            sp[upos] = s_kv[i];
-          }
-          a.st[op] = 11;  // PMDFC_ST_UPDATED
-          lines += ((((uint32_t)upos - wi0) & (kSlots - 1)) >> 2) + 1;
-          s_pend[i] = 0;
-          continue;
-        }
-      }
-      const int pos = window_first_free(bm[wi], bm[(wi + 1) & 31u], wi0);
-      if (pos >= 0) {
-        bm[(uint32_t)pos >> 5] |= 1u << ((uint32_t)pos & 31u);
-        dirty = true;
+    const uint32_t wi0 = sk_home(skq) * 4u;
+    const uint32_t wi = wi0 >> 5;
+    if (a.upsert) {
+      // last-writer-wins: the key's own slot takes the pair if it has one
+      const uint64_t key = chunk_key<REG>(S, i);
+      const int upos = upsert_slot<REG>(a, S, sp, bm, q0, q, key, op, wi0);
+      if (upos >= 0) {
+        S.pos[i] = (uint16_t)upos;
         if (MIXED) {
-          if (s_kv[i].x == memo_k) memo_k = kInvalid;
-          sp[pos] = s_kv[i];
-          a.st[op] = 2;  // PMDFC_ST_INSERTED (insert-only batches: preset by k_part)
-          if (a.upsert) s_pos[i] = (uint16_t)pos;  // a later insert of the key in this run updates it
-        } else {
-          s_pos[i] = (uint16_t)pos;
+          if (key == memo_k) memo_k = kInvalid;
+          sp[upos] = S.kv[i];
         }
-        lines += ((((uint32_t)pos - wi0) & (kSlots - 1)) >> 2) + 1;
-        s_pend[i] = 0;
+        a.st[op] = 11;  // PMDFC_ST_UPDATED
+        lines += ((((uint32_t)upos - wi0) & (kSlots - 1)) >> 2) + 1;
+        S.pend[i] = 0;
         continue;
       }
-      // window full.  The reference would split forever if all 32 entries
-      // carry this key's full hash: UNSPLITTABLE.
-      bool same;
-      if constexpr (REG) same = window_all_same_reg(sp, s_sk, s_pos, s_key, q0, q, i, wi0);
-      else same = window_all_same(MIXED, sp, s_sk, s_pos, s_kv, q0, q, i, wi0);
-      if (same || L + 1 > kMaxDepth) {
-        a.st[op] = same ? 4 : 5;  // PMDFC_ST_UNSPLITTABLE / PMDFC_ST_DEPTH_LIMIT
-        s_pend[i] = 0;
-        continue;
+    }
+    const int pos = window_first_free(bm[wi], bm[(wi + 1) & 31u], wi0);
+    if (pos >= 0) {
+      bm[(uint32_t)pos >> 5] |= 1u << ((uint32_t)pos & 31u);
+      dirty = true;
+      if (MIXED) {
+        if (S.kv[i].x == memo_k) memo_k = kInvalid;
+        sp[pos] = S.kv[i];
+        a.st[op] = 2;  // PMDFC_ST_INSERTED (insert-only batches: preset by k_part)
+        if (a.upsert) S.pos[i] = (uint16_t)pos;  // a later insert of the key in this run updates it
+      } else {
+        S.pos[i] = (uint16_t)pos;
       }
-      if (!FINAL) {
-        if (a.full) {  // a split round ran out of segment ids or pool
-          a.st[op] = 6;  // PMDFC_ST_CAPACITY
-          s_pend[i] = 0;
-          continue;
-        }
-        // request the split; park the rest of the run (batch order is
-        // restored by the next pass's sort), nothing of it runs ahead
-        const uint32_t ri = a.noreq ? kSplitCap : atomicAdd(s_nreq, 1u);
-        if (ri < kSplitCap) {
-          const uint32_t x = sub_index(hash64(key_of(i)), a.sbits, a.p1, a.db);
-          a.req[ri] = make_uint2(seg | (L << 27), x);
-          a.reqop[ri] = op;
-          atomicMax(s_need, L + 1 - lbase);
-        }
-        if constexpr (!REG) {
-          const uint32_t k0 = atomicAdd(s_nsplit, q1 - q);
-          for (uint32_t qq = q; qq < q1; ++qq) {
-            const uint32_t i2 = sk_item(s_sk[qq]);
-            wl_kv[k0 + (qq - q)] = s_kv[i2];
-            wl_op[k0 + (qq - q)] = s_op[i2];
-          }
-        } else {  // the rest of the run stays pending; its owner lanes park it
-          for (uint32_t qq = q; qq < q1; ++qq) s_pend[sk_item(s_sk[qq])] = 2;
-        }
-        waited += q1 - q;
-        break;
-      }
-      const uint32_t si = atomicAdd(s_nsplit, 1u);
-      if (si >= kSplitCap) {
-        waited += q1 - q;  // split queue full: the run retries next round
-        break;
-      }
-      const uint32_t c1 = atomicAdd(&a.ctl->nsegs, 1u);
-      if (c1 >= a.max_segments) {
-        s_split[si] = ~0ULL;
+      lines += ((((uint32_t)pos - wi0) & (kSlots - 1)) >> 2) + 1;
+      S.pend[i] = 0;
+      continue;
+    }
+    // window full.  The reference would split forever if all 32 entries
+    // carry this key's full hash: UNSPLITTABLE.
+    bool same;
+    if constexpr (REG) same = window_all_same_reg(sp, S.sk, S.pos, S.key, q0, q, i, wi0);
+    else same = window_all_same(MIXED, sp, S.sk, S.pos, S.kv, q0, q, i, wi0);
+    if (same || L + 1 > kMaxDepth) {
+      a.st[op] = same ? 4 : 5;  // PMDFC_ST_UNSPLITTABLE / PMDFC_ST_DEPTH_LIMIT
+      S.pend[i] = 0;
+      continue;
+    }
+    if (!FINAL) {
+      if (a.full) {  // a split round ran out of segment ids or pool
         a.st[op] = 6;  // PMDFC_ST_CAPACITY
-        s_pend[i] = 0;
+        S.pend[i] = 0;
         continue;
       }
-      s_split[si] = (uint64_t)i | ((uint64_t)L << 16) | ((uint64_t)c1 << 21);
-      atomicMax(s_need, L + 1 - lbase);
+      // request the split; park the rest of the run (batch order is
+      // restored by the next pass's sort), nothing of it runs ahead
+      const uint32_t ri = a.noreq ? kSplitCap : atomicAdd(&S.nreq, 1u);
+      if (ri < kSplitCap) {
+        const uint32_t x = sub_index(hash64(chunk_key<REG>(S, i)), a.sbits, a.p1, a.db);
+        a.req[ri] = make_uint2(seg | (L << 27), x);
+        a.reqop[ri] = op;
+        atomicMax(&S.need, L + 1 - lbase);
+      }
+      if constexpr (!REG) {
+        const uint32_t k0 = atomicAdd(&S.nsplit, q1 - q);
+        for (uint32_t qq = q; qq < q1; ++qq) {
+          const uint32_t i2 = sk_item(S.sk[qq]);
+          a.wl_kv[k0 + (qq - q)] = S.kv[i2];
+          a.wl_op[k0 + (qq - q)] = S.op[i2];
+        }
+      } else {  // the rest of the run stays pending; its owner lanes park it
+        for (uint32_t qq = q; qq < q1; ++qq) S.pend[sk_item(S.sk[qq])] = 2;
+      }
       waited += q1 - q;
-      break;  // the rest of the run waits for the split
+      break;
     }
-    if (dirty) {
-      uint32_t* o = a.occ + (size_t)seg * 32u;
+    const uint32_t si = atomicAdd(&S.nsplit, 1u);
+    if (si >= kSplitCap) {
+      waited += q1 - q;  // split queue full: the run retries next round
+      break;
+    }
+    const uint32_t c1 = atomicAdd(&a.ctl->nsegs, 1u);
+    if (c1 >= a.max_segments) {
+      S.split[si] = ~0ULL;
+      a.st[op] = 6;  // PMDFC_ST_CAPACITY
+      S.pend[i] = 0;
+      continue;
+    }
+    S.split[si] = (uint64_t)i | ((uint64_t)L << 16) | ((uint64_t)c1 << 21);
+    atomicMax(&S.need, L + 1 - lbase);
+    waited += q1 - q;
+    break;  // the rest of the run waits for the split
+  }
+  if (dirty) {
+    uint32_t* o = a.occ + (size_t)seg * 32u;
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        *reinterpret_cast<uint4*>(o + 4 * j) = make_uint4(bm[4 * j], bm[4 * j + 1], bm[4 * j + 2], bm[4 * j + 3]);
-    }
-    if (a.stamp && (__lane_id() & 63u) == 0) a.stamp[15] = wall_clock64();
-    return make_uint2(lines, waited);
+    for (int j = 0; j < 8; ++j)
+      *reinterpret_cast<uint4*>(o + 4 * j) = make_uint4(bm[4 * j], bm[4 * j + 1], bm[4 * j + 2], bm[4 * j + 3]);
+  }
+  stamp(a.stamp, kBsRunEnd, (__lane_id() & 63u) == 0);
+  return make_uint2(lines, waited);
 }
 
 // Sub-directory growth to `need` bits: a new pool region, new[i] = old[i >> k]
@@ -1334,14 +1392,14 @@ __device__ __forceinline__ void dir_split(const BucketArgs& a, uint32_t off, uin
 // (k_split already moved the entries): grow the sub-directory if they need
 // it, then point the children's directory entries at them.
 __device__ __forceinline__ void commit_splits(const BucketArgs& a, uint32_t w, uint32_t& off, uint32_t& db,
-                                              uint32_t& c_splits, uint32_t& c_grow, uint32_t& max_ld) {
+                                              WaveStat& c) {
   const uint32_t ng = a.ngrant[w];
   if (!ng) return;
   const uint32_t db0 = db;
   const uint32_t nd = a.need[w];
   if (nd > db) {
     grow_subdir(a, w, a.newoff[w], nd, off, db);
-    ++c_grow;
+    ++c.grow;
   }
   const uint32_t cb = a.gbase[w];
   const uint2* rq = a.req + (size_t)w * kSplitCap;
@@ -1349,10 +1407,10 @@ __device__ __forceinline__ void commit_splits(const BucketArgs& a, uint32_t w, u
     const uint2 r = rq[i];
     const uint32_t L = r.x >> 27;
     dir_split(a, off, db, r.y << (db - db0), r.x & ((1u << 27) - 1), cb + i, L);
-    max_ld = max(max_ld, L + 1);
+    c.max_ld = max(c.max_ld, L + 1);
   }
   __builtin_amdgcn_s_waitcnt(0);
-  c_splits += ng;
+  c.splits += ng;
   if ((__lane_id() & 63u) == 0) a.ngrant[w] = 0;
 }
 
@@ -1534,37 +1592,165 @@ __device__ __forceinline__ uint32_t fc_full(const BucketArgs& a, uint32_t full, 
 // words (loaded by the caller for that probe).  An insert whose key is
 // stored claims nothing: it overwrites its slot (PMDFC_ST_UPDATED) unless its
 // segment splits before it in the batch, then it is parked like the others.
+// A lane's kPer ops as fast_claim reads them: key, value, rop word, whether
+// the slot holds an insert, its directory entry, home line and sub-directory
+// index (references: the arrays stay the caller's registers)
+struct LaneOps {
+  const uint64_t (&rk)[kPer], (&rv)[kPer];
+  const uint32_t (&rop)[kPer];
+  const bool (&pq)[kPer];
+  const uint32_t (&e8)[kPer], (&home8)[kPer], (&x8)[kPer];
+};
+// fast_claim's scratch (FcLayout) as pointers
+template <uint32_t NL, uint32_t NB>
+struct FcScr {
+  using FL = FcLayout<NL, NB>;
+  uint32_t *hm, *dm, *cnt, *dst, *bfull, *opk, *snap, *unres;
+  uint16_t* res;
+  uint8_t *slot8, *binp;
+  __device__ __forceinline__ explicit FcScr(uint32_t* sc)
+      : hm(sc + FL::Hm), dm(sc + FL::Dm), cnt(sc + FL::Cnt), dst(sc + FL::Dst), bfull(sc + FL::Full),
+        opk(sc + FL::Opk), snap(sc + FL::Snap), unres(sc + FL::Unres), res(reinterpret_cast<uint16_t*>(sc + FL::Res)),
+        slot8(reinterpret_cast<uint8_t*>(sc + FL::Slot)), binp(reinterpret_cast<uint8_t*>(sc + FL::Binp)) {}
+};
+
+// Step 3 of fast_claim: the ntot dependent inserts resolve in rounds, one list
+// entry per lane (the list is usually shorter than a wave): first each
+// entry's earlier overlapping entries of its segment as a mask over the
+// segment's list, then rounds in which an entry whose mask is resolved
+// decides (F.res; a full window lowers F.bfull to its op index).
+template <uint32_t NL, uint32_t NB>
+__device__ __forceinline__ void fc_resolve(const FcScr<NL, NB>& F, uint32_t ntot, uint64_t* srow) {
+  const uint32_t lane = __lane_id() & 63u;
+  constexpr int kLp = (int)NL / 64;
+  uint32_t dmask[kLp], lres[kLp];
+#pragma unroll
+  for (int u = 0; u < kLp; ++u) {
+    const uint32_t p = (uint32_t)u * 64u + lane;
+    dmask[u] = 0;
+    lres[u] = 1;  // (no entry: nothing to resolve)
+    if (p >= ntot) continue;
+    lres[u] = 0;
+    const uint32_t v = F.opk[p], xc = F.binp[p], q0 = F.dst[xc], n = F.cnt[xc];
+    const uint32_t op = v >> 8, h = v & 0xFFu;
+    for (uint32_t q = 0; q < n; q += 4) {  // 4 independent LDS reads in flight
+      uint32_t vq[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) vq[t] = q + t < n ? F.opk[q0 + q + t] : 0xFFFFFFFFu;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const uint32_t dl = ((vq[t] & 0xFFu) - h) & 0xFFu;
+        if ((vq[t] >> 8) < op && (dl <= 7u || dl >= 249u)) dmask[u] |= 1u << (q + t);
+      }
+    }
+  }
+  stamp(srow, kBsFcMasks, lane == 0);
+  uint32_t nrounds = 0;
+  for (uint32_t round = 0; round <= kDepMax; ++round) {
+    ++nrounds;
+    bool blocked_any = false;
+    uint32_t nr[kLp];
+#pragma unroll
+    for (int u = 0; u < kLp; ++u) {
+      nr[u] = 0;
+      const uint32_t p = (uint32_t)u * 64u + lane;
+      if (lres[u]) continue;
+      const uint32_t xc = F.binp[p];
+      if (dmask[u] & F.unres[xc]) {
+        blocked_any = true;
+        continue;
+      }
+      const uint32_t v = F.opk[p], wo = (v & 0xFFu) * 4u, q0 = F.dst[xc];
+      uint32_t occw = F.snap[p];
+      bool park = false;
+      for (uint32_t m = dmask[u]; m; m &= m - 1u) {
+        const uint32_t rq = F.res[q0 + (uint32_t)__builtin_ctz(m)];
+        const uint32_t ds = ((rq & (kSlots - 1)) - wo) & (kSlots - 1);
+        park |= (rq & (kFrFull | kFrPark)) != 0;
+        if ((rq & kFrClaim) && ds < kWindow) occw |= 1u << ds;
+      }
+      if (park) {  // behind an earlier full window of its segment: waits with it
+        nr[u] = kFrPark;
+      } else if (~occw) {
+        nr[u] = kFrClaim | ((wo + (uint32_t)__builtin_ctz(~occw)) & (kSlots - 1));
+      } else {
+        nr[u] = kFrFull;
+        atomicMin(&F.bfull[xc], v >> 8);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int u = 0; u < kLp; ++u) {
+      if (!nr[u]) continue;
+      const uint32_t p = (uint32_t)u * 64u + lane, xc = F.binp[p];
+      F.res[p] = (uint16_t)nr[u];
+      atomicAnd(&F.unres[xc], ~(1u << (p - F.dst[xc])));
+      lres[u] = nr[u];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (!__ballot(blocked_any)) break;
+  }
+  stamp(srow, kBsFcResolved, lane == 0);
+  if (srow && lane == 0) srow[kBsFcRounds] = nrounds | ((uint64_t)ntot << 16);
+}
+
+// Step 4 of fast_claim: every decision is made (st[j]: kFr* | slot of the
+// lane's insert j; pc[j]: it claims a slot).  What precedes its segment's
+// split is committed, the rest parked; the insert at the split requests it.
+template <bool UPS, uint32_t NL, uint32_t NB, class BinF>
+__device__ __forceinline__ void fc_commit(const BucketArgs& a, uint32_t w, const FcScr<NL, NB>& F, const LaneOps& o,
+                                          const bool (&pc)[kPer], const uint32_t (&st)[kPer], BinF bin,
+                                          ulonglong2* wl_kv, uint32_t* wl_op, uint32_t* s_nsplit, uint32_t* s_nreq,
+                                          uint32_t* s_need, WaveStat& c, const uint32_t* upd) {
+  const uint32_t lbase = a.sbits + a.p1;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    if (!o.pq[j]) continue;
+    const uint32_t op = o.rop[j] & kOpMask, bf = F.bfull[bin(j)];
+    const uint32_t r = st[j] & 0xFFFFu;
+    const uint32_t seg = de_seg(o.e8[j]);
+    if (op >= bf || (r & kFrPark)) {
+      if (op == bf) {  // this insert's full window splits the segment
+        const uint32_t L = de_ld(o.e8[j]);
+        const uint32_t ri = a.mode == 2 ? kSplitCap : atomicAdd(s_nreq, 1u);
+        if (ri < kSplitCap) {
+          a.req[(size_t)w * kSplitCap + ri] = make_uint2(seg | (L << 27), o.x8[j]);
+          a.reqop[(size_t)w * kSplitCap + ri] = op;
+          atomicMax(s_need, L + 1 - lbase);
+        }
+      }
+      const uint32_t k = atomicAdd(s_nsplit, 1u);
+      wl_kv[k] = make_ulonglong2(o.rk[j], o.rv[j]);
+      wl_op[k] = o.rop[j];
+      ++c.waited;
+    } else if (r & kFrClaim) {
+      const uint32_t sl = r & (kSlots - 1);
+      a.pairs[(size_t)seg * kSlots + sl] = make_ulonglong2(o.rk[j], o.rv[j]);
+      atomicOr(a.occ + (size_t)seg * 32u + (sl >> 5), 1u << (sl & 31u));
+      c.lines += (((sl - o.home8[j] * 4u) & (kSlots - 1)) >> 2) + 1u;
+    } else if (UPS && !pc[j]) {  // its key is stored: overwrite in place
+      const uint32_t sl = upd[j];
+      a.pairs[(size_t)seg * kSlots + sl] = make_ulonglong2(o.rk[j], o.rv[j]);
+      a.st[op] = 11;  // PMDFC_ST_UPDATED
+      c.lines += (((sl - o.home8[j] * 4u) & (kSlots - 1)) >> 2) + 1u;
+    }
+  }
+}
+
 template <uint32_t NL, uint32_t NB, bool UPS = false, class BinF>
 __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint32_t* sc,
                                            const uint64_t* s_key, ulonglong2* wl_kv, uint32_t* wl_op,
                                            uint32_t* s_nsplit, uint32_t* s_nreq, uint32_t* s_need,
-                                           const uint64_t (&rk)[kPer], const uint64_t (&rv)[kPer],
-                                           const uint32_t (&rop)[kPer], const bool (&pq)[kPer],
-                                           const uint32_t (&e8)[kPer], const uint32_t (&home8)[kPer],
-                                           const uint32_t (&x8)[kPer], BinF bin, uint32_t& c_runs,
-                                           uint32_t& c_lines, uint32_t& c_waited, uint64_t* stamp,
+                                           const LaneOps& o, BinF bin, WaveStat& c, uint64_t* srow,
                                            const uint32_t* upd = nullptr, const uint32_t* occw = nullptr) {
-  using FL = FcLayout<NL, NB>;
   const uint32_t lane = __lane_id() & 63u;
-#define FC_STAMP(ph) \
-  if (stamp && lane == 0) stamp[ph] = wall_clock64()
-  const uint32_t lbase = a.sbits + a.p1;
   const uint32_t full = a.ctl->full;
-  uint32_t* const hm = sc + FL::Hm;
-  uint32_t* const dm = sc + FL::Dm;
-  uint32_t* const cnt = sc + FL::Cnt;
-  uint32_t* const dst = sc + FL::Dst;
-  uint32_t* const bfull = sc + FL::Full;
-  uint32_t* const opk = sc + FL::Opk;
-  uint32_t* const snap = sc + FL::Snap;
-  uint16_t* const res = reinterpret_cast<uint16_t*>(sc + FL::Res);
-  uint8_t* const slot8 = reinterpret_cast<uint8_t*>(sc + FL::Slot);
-  uint8_t* const binp = reinterpret_cast<uint8_t*>(sc + FL::Binp);
-  uint32_t* const unres = sc + FL::Unres;
+  const FcScr<NL, NB> F(sc);
+  uint32_t *const hm = F.hm, *const dm = F.dm, *const cnt = F.cnt, *const dst = F.dst, *const bfull = F.bfull;
   // claimers: the inserts that take a slot (UPS: not those whose key is stored)
   bool pc[kPer];
 #pragma unroll
-  for (int j = 0; j < kPer; ++j) pc[j] = pq[j] && (!UPS || upd[j] == 0xFFFFu);
+  for (int j = 0; j < kPer; ++j) pc[j] = o.pq[j] && (!UPS || upd[j] == 0xFFFFu);
   // each insert's two occupancy words (its window), in flight during the LDS work
   uint32_t olo[kPer], ohi[kPer];
 #pragma unroll
@@ -1574,8 +1760,8 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
       olo[j] = occw[2 * j];
       ohi[j] = occw[2 * j + 1];
     } else {
-      const uint32_t* og = a.occ + (size_t)de_seg(e8[j]) * 32u;
-      const uint32_t wi = home8[j] >> 3;
+      const uint32_t* og = a.occ + (size_t)de_seg(o.e8[j]) * 32u;
+      const uint32_t wi = o.home8[j] >> 3;
       olo[j] = ld_u32_l2(og + wi);
       ohi[j] = ld_u32_l2(og + ((wi + 1u) & 31u));
     }
@@ -1591,13 +1777,13 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
   uint32_t st[kPer];  // per insert: result (kFr* | slot or status) | list position << 16 | dependent << 24
 #pragma unroll
   for (int j = 0; j < kPer; ++j)
-    if (pc[j]) st[j] = atomicOr(&hm[bin(j) * 8u + (home8[j] >> 5)], 1u << (home8[j] & 31u));
+    if (pc[j]) st[j] = atomicOr(&hm[bin(j) * 8u + (o.home8[j] >> 5)], 1u << (o.home8[j] & 31u));
 #pragma unroll
   for (int j = 0; j < kPer; ++j)
-    if (pc[j] && ((st[j] >> (home8[j] & 31u)) & 1u)) atomicOr(&dm[bin(j) * 8u + (home8[j] >> 5)], 1u << (home8[j] & 31u));
+    if (pc[j] && ((st[j] >> (o.home8[j] & 31u)) & 1u)) atomicOr(&dm[bin(j) * 8u + (o.home8[j] >> 5)], 1u << (o.home8[j] & 31u));
   __builtin_amdgcn_wave_barrier();
-  FC_STAMP(4);
-  if (stamp && lane == 0) stamp[2] = 0;  // (no sort stamp: phase_stamps.py tells the paths apart)
+  stamp(srow, kBsBinned, lane == 0);
+  if (srow && lane == 0) srow[kBsOrdered] = 0;  // (no sort stamp: phase_stamps.py tells the paths apart)
   // 2. independent inserts claim now; dependent ones are counted per segment
   constexpr uint32_t kDep = 1u << 24;
   uint64_t fk = 0;  // first window key of this lane's first independent full window
@@ -1606,7 +1792,7 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
   for (int j = 0; j < kPer; ++j) {
     st[j] = 0;
     if (!pc[j]) continue;
-    const uint32_t h = home8[j], xc = bin(j), base = xc * 8u, l0 = (h - 7u) & 255u;
+    const uint32_t h = o.home8[j], xc = bin(j), base = xc * 8u, l0 = (h - 7u) & 255u;
     const uint32_t wo = h * 4u;
     const uint32_t win = __builtin_amdgcn_alignbit(ohi[j], olo[j], wo & 31u);  // bit t: slot wo + t taken
     // lines another insert's window may claim in: its home within 7 lines
@@ -1624,9 +1810,9 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
       st[j] = kFrClaim | ((wo + (uint32_t)__builtin_ctz(~win)) & (kSlots - 1));
     } else {
       st[j] = kFrFull;
-      atomicMin(&bfull[xc], rop[j] & kOpMask);
+      atomicMin(&bfull[xc], o.rop[j] & kOpMask);
       if (fkj < 0) {  // the window's first key, for the rarely true UNSPLITTABLE test below
-        fk = ld_pair_l2(a.pairs + (size_t)de_seg(e8[j]) * kSlots + wo).x;
+        fk = ld_pair_l2(a.pairs + (size_t)de_seg(o.e8[j]) * kSlots + wo).x;
         fkj = j;
       }
     }
@@ -1645,165 +1831,49 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
     runs = (uint32_t)__popcll(__ballot(any != 0));
   }
   __builtin_amdgcn_wave_barrier();
-  FC_STAMP(5);
+  stamp(srow, kBsBatchOrder, lane == 0);
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     if (!(st[j] & kDep)) continue;
     const uint32_t xc = bin(j), p = dst[xc] + ((st[j] >> 16) & 0xFFu);
     st[j] = kDep | (p << 16);
-    opk[p] = ((rop[j] & kOpMask) << 8) | home8[j];
-    snap[p] = __builtin_amdgcn_alignbit(ohi[j], olo[j], (home8[j] * 4u) & 31u);  // the window before the pass
-    res[p] = 0;
-    slot8[p] = (uint8_t)((uint32_t)j * 64u + lane);
-    binp[p] = (uint8_t)xc;
+    F.opk[p] = ((o.rop[j] & kOpMask) << 8) | o.home8[j];
+    F.snap[p] = __builtin_amdgcn_alignbit(ohi[j], olo[j], (o.home8[j] * 4u) & 31u);  // the window before the pass
+    F.res[p] = 0;
+    F.slot8[p] = (uint8_t)((uint32_t)j * 64u + lane);
+    F.binp[p] = (uint8_t)xc;
   }
-  if (lane < NB) unres[lane] = cb >= 32 ? 0xFFFFFFFFu : (1u << cb) - 1u;
+  if (lane < NB) F.unres[lane] = cb >= 32 ? 0xFFFFFFFFu : (1u << cb) - 1u;
   __builtin_amdgcn_wave_barrier();
-  // 3. dependent inserts resolve in rounds, one list entry per lane (the
-  // list is usually shorter than a wave): first each entry's earlier
-  // overlapping entries of its segment as a mask over the segment's list,
-  // then rounds in which an entry whose mask is resolved decides
-  constexpr int kLp = (int)NL / 64;
-  uint32_t dmask[kLp], lres[kLp];
-#pragma unroll
-  for (int u = 0; u < kLp; ++u) {
-    const uint32_t p = (uint32_t)u * 64u + lane;
-    dmask[u] = 0;
-    lres[u] = 1;  // (no entry: nothing to resolve)
-    if (p >= ntot) continue;
-    lres[u] = 0;
-    const uint32_t v = opk[p], xc = binp[p], q0 = dst[xc], n = cnt[xc];
-    const uint32_t op = v >> 8, h = v & 0xFFu;
-    for (uint32_t q = 0; q < n; q += 4) {  // 4 independent LDS reads in flight
-      uint32_t vq[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) vq[t] = q + t < n ? opk[q0 + q + t] : 0xFFFFFFFFu;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const uint32_t dl = ((vq[t] & 0xFFu) - h) & 0xFFu;
-        if ((vq[t] >> 8) < op && (dl <= 7u || dl >= 249u)) dmask[u] |= 1u << (q + t);
-      }
-    }
-  }
-  FC_STAMP(10);
-  uint32_t nrounds = 0;
-  for (uint32_t round = 0; round <= kDepMax; ++round) {
-    ++nrounds;
-    bool blocked_any = false;
-    uint32_t nr[kLp];
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      nr[u] = 0;
-      const uint32_t p = (uint32_t)u * 64u + lane;
-      if (lres[u]) continue;
-      const uint32_t xc = binp[p];
-      if (dmask[u] & unres[xc]) {
-        blocked_any = true;
-        continue;
-      }
-      const uint32_t v = opk[p], wo = (v & 0xFFu) * 4u, q0 = dst[xc];
-      uint32_t occw = snap[p];
-      bool park = false;
-      for (uint32_t m = dmask[u]; m; m &= m - 1u) {
-        const uint32_t rq = res[q0 + (uint32_t)__builtin_ctz(m)];
-        const uint32_t ds = ((rq & (kSlots - 1)) - wo) & (kSlots - 1);
-        park |= (rq & (kFrFull | kFrPark)) != 0;
-        if ((rq & kFrClaim) && ds < kWindow) occw |= 1u << ds;
-      }
-      if (park) {  // behind an earlier full window of its segment: waits with it
-        nr[u] = kFrPark;
-      } else if (~occw) {
-        nr[u] = kFrClaim | ((wo + (uint32_t)__builtin_ctz(~occw)) & (kSlots - 1));
-      } else {
-        nr[u] = kFrFull;
-        atomicMin(&bfull[xc], v >> 8);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int u = 0; u < kLp; ++u) {
-      if (!nr[u]) continue;
-      const uint32_t p = (uint32_t)u * 64u + lane, xc = binp[p];
-      res[p] = (uint16_t)nr[u];
-      atomicAnd(&unres[xc], ~(1u << (p - dst[xc])));
-      lres[u] = nr[u];
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (!__ballot(blocked_any)) break;
-  }
-  FC_STAMP(12);
-  if (stamp && lane == 0) stamp[11] = nrounds | ((uint64_t)ntot << 16);
+  // 3. dependent inserts resolve in rounds
+  fc_resolve(F, ntot, srow);
   // owners take their dependent results
 #pragma unroll
   for (int j = 0; j < kPer; ++j)
-    if (st[j] & kDep) st[j] |= res[(st[j] >> 16) & 0xFFu];
+    if (st[j] & kDep) st[j] |= F.res[(st[j] >> 16) & 0xFFu];
   // the first full window of a segment splits it -- unless the insert fails
   // instead (UNSPLITTABLE / DEPTH_LIMIT / CAPACITY, rare): then later inserts
   // go on past it, which the sorted run loop handles
   bool fails = false;
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
-    if (!pc[j] || (rop[j] & kOpMask) != bfull[bin(j)]) continue;
+    if (!pc[j] || (o.rop[j] & kOpMask) != bfull[bin(j)]) continue;
     const uint32_t xc = bin(j), q0 = (st[j] & kDep) ? dst[xc] : 0u, n = (st[j] & kDep) ? cnt[xc] : 0u;
-    if (fkj == j && hash64(fk) != hash64(rk[j])) {  // not all one hash: splittable
-      fails |= de_ld(e8[j]) + 1 > kMaxDepth || full;
+    if (fkj == j && hash64(fk) != hash64(o.rk[j])) {  // not all one hash: splittable
+      fails |= de_ld(o.e8[j]) + 1 > kMaxDepth || full;
       continue;
     }
-    fails |= fc_full(a, full, e8[j], rk[j], home8[j] * 4u, res, slot8, s_key, q0, n) != kFrSplit;
+    fails |= fc_full(a, full, o.e8[j], o.rk[j], o.home8[j] * 4u, F.res, F.slot8, s_key, q0, n) != kFrSplit;
   }
   if (__ballot(fails)) return false;  // still nothing written
-  FC_STAMP(6);
+  stamp(srow, kBsRunsDone, lane == 0);
   // 4. commit what precedes each segment's split, park the rest
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    if (!pq[j]) continue;
-    const uint32_t op = rop[j] & kOpMask, bf = bfull[bin(j)];
-    const uint32_t r = st[j] & 0xFFFFu;
-    const uint32_t seg = de_seg(e8[j]);
-    if (op >= bf || (r & kFrPark)) {
-      if (op == bf) {  // this insert's full window splits the segment
-        const uint32_t L = de_ld(e8[j]);
-        const uint32_t ri = a.mode == 2 ? kSplitCap : atomicAdd(s_nreq, 1u);
-        if (ri < kSplitCap) {
-          a.req[(size_t)w * kSplitCap + ri] = make_uint2(seg | (L << 27), x8[j]);
-          a.reqop[(size_t)w * kSplitCap + ri] = op;
-          atomicMax(s_need, L + 1 - lbase);
-        }
-      }
-      const uint32_t k = atomicAdd(s_nsplit, 1u);
-      wl_kv[k] = make_ulonglong2(rk[j], rv[j]);
-      wl_op[k] = rop[j];
-      ++c_waited;
-    } else if (r & kFrClaim) {
-      const uint32_t sl = r & (kSlots - 1);
-      a.pairs[(size_t)seg * kSlots + sl] = make_ulonglong2(rk[j], rv[j]);
-      atomicOr(a.occ + (size_t)seg * 32u + (sl >> 5), 1u << (sl & 31u));
-      c_lines += (((sl - home8[j] * 4u) & (kSlots - 1)) >> 2) + 1u;
-    } else if (UPS && !pc[j]) {  // its key is stored: overwrite in place
-      const uint32_t sl = upd[j];
-      a.pairs[(size_t)seg * kSlots + sl] = make_ulonglong2(rk[j], rv[j]);
-      a.st[op] = 11;  // PMDFC_ST_UPDATED
-      c_lines += (((sl - home8[j] * 4u) & (kSlots - 1)) >> 2) + 1u;
-    }
-  }
-  if (lane == 0) c_runs += runs;
-  FC_STAMP(3);
-#undef FC_STAMP
+  fc_commit<UPS>(a, w, F, o, pc, st, bin, wl_kv, wl_op, s_nsplit, s_nreq, s_need, c, upd);
+  if (lane == 0) c.runs += runs;
+  stamp(srow, kBsWritten, lane == 0);
   return true;
 }
 
-// k_apply (FINAL = false, high occupancy, no split code): one round per
-// directory bucket; a run blocked by a full window requests a split and parks
-// the rest of the run.  mode 0 takes the bucket's records of the batch, mode 1
-// its parked ops (after committing the last split round's splits).
-// k_bucket (FINAL = true): buckets with parked ops, granted splits or too many
-// ops for one chunk; loops rounds with inline splits until its ops are done.
-constexpr uint32_t kBigBucket = 0xFFFFFFFFu;
-
-constexpr uint32_t kLdsDir = 128;  // k_apply: sub-directories up to this size are read into LDS
-
-// LDS of one bucket wave; the apply pass (no splits) carries no split state,
-// which keeps its footprint, and so its occupancy, lower.
 // The first apply pass of a batch (parity p) resets the previous batch's
 // grant shards and final-pass count (parity p ^ 1): every pass that read
 // them ran before it on the stream.
@@ -1815,60 +1885,688 @@ __device__ __forceinline__ void clear_other_parity(const BucketArgs& a) {
   if (lane == 2 * kGShards + 2) a.ctl->anydecl[q] = 0;
 }
 
-template <bool FINAL, bool REG>
-struct BucketLds {
-  uint32_t u[FINAL ? kUnionWords : kBmWords];  // run phase: per-lane bitmaps; split phase: scratch
-  uint64_t sk[kCW];       // sort keys of the pending ops
-  ulonglong2 kv[REG ? 1 : kCW];   // {key, value} of each chunk slot (REG: in registers)
-  uint64_t key[REG ? kCW : 1];    // REG: the key of each chunk slot
-  uint32_t op[REG ? 1 : kCW];     // rop word of each chunk slot (REG: in registers)
-  uint16_t pos[kCW];      // insert-only: slot claimed this round, 0xFFFF none
-  uint16_t runq[kCW + 1];
-  uint8_t L[kCW];         // local depth of the op's segment | Get << 7
-  uint8_t pend[kCW];
-  uint64_t split[FINAL ? kSplitCap : 1];
-  uint32_t dir[FINAL ? 1 : kLdsDir];           // apply pass: the bucket's sub-directory
-  uint32_t nsplit, nreq, need;
+// ---- what every first pass of a batch does (bucket_body<.., FIRST> in mode
+// 0 and apply_fast), one copy each
+
+// The next batch's cursors start at zero, and the previous batch's per-parity
+// words are reset.
+__device__ __forceinline__ void first_pass_clears(const BucketArgs& a, uint32_t w) {
+  const uint32_t lane = __lane_id() & 63u;
+  const uint32_t pb = w >> a.sbb, sub = w & ((1u << a.sbb) - 1);
+  if (a.clear_next) {
+    if (sub == 0 && lane < kPartSubs) a.cursor_next[(lane << (a.p1 - a.sbb)) + pb] = 0;
+    if (w == 0 && lane == 0) *a.ovf_next = 0;
+  }
+  if (w == 0) clear_other_parity(a);
+}
+
+// 32 records of each of the partition bucket's kPartSubs sub-regions, one per
+// lane and slot: slot u of lane l is record 32 * half + (l & 31) of sub-region
+// 2u + l / 32 (clamped to the sub-region: the count decides what is valid).
+// Loaded before anything is known about the bucket, so that they share one
+// round trip with the header and cursor loads.
+constexpr int kPre = 4;  // 4 x 64 = 256 records
+static_assert(kPre * 64 == 32 * kPartSubs, "prefetch: 32 records per sub-region");
+struct PreRecs {
+  uint32_t op[kPre];
+  uint64_t k[kPre], v[kPre];
 };
-// the REG collect path stages kCW {key, value} pairs across u and sk
-using BucketLdsReg = BucketLds<false, true>;
-static_assert(offsetof(BucketLdsReg, sk) == sizeof(uint32_t) * kBmWords &&
-                  sizeof(uint32_t) * kBmWords + sizeof(uint64_t) * kCW >= sizeof(ulonglong2) * kCW,
-              "REG collect staging spans u and sk");
+__device__ __forceinline__ void prefetch_records(const BucketArgs& a, uint32_t pb, uint32_t half, PreRecs& pr) {
+  const uint32_t lane = __lane_id() & 63u;
+  const uint64_t rb0 = (uint64_t)pb * a.cap;
+#pragma unroll
+  for (int u = 0; u < kPre; ++u) {
+    const uint32_t jj = (uint32_t)u * 64u + lane;
+    const uint64_t j = rb0 + (uint64_t)(jj >> 5) * a.capx + min(half * 32u + (jj & 31u), a.capx - 1u);
+    pr.op[u] = a.rop[j];
+    const ulonglong2 kv = a.rkv[j];
+    pr.k[u] = kv.x;
+    pr.v[u] = kv.y;
+  }
+}
+// whether slot u of this lane holds a record of sub-bucket `sub` (csub: below)
+__device__ __forceinline__ bool pre_valid(const BucketArgs& a, const PreRecs& pr, int u, uint32_t half, uint32_t csub,
+                                          uint32_t sub) {
+  const uint32_t jj = (uint32_t)u * 64u + (__lane_id() & 63u);
+  const uint32_t cs = (uint32_t)__shfl((int)csub, (int)(jj >> 5));
+  return half * 32u + (jj & 31u) < cs && ((pr.op[u] >> 22) & ((1u << a.sbb) - 1)) == sub;
+}
+// The valid prefetched records appended to kv[] / op[] at m (ballot and
+// prefix; nothing stored past `cap`).  Returns the new count, which may
+// exceed cap.
+__device__ __forceinline__ uint32_t compact_prefetched(const BucketArgs& a, const PreRecs& pr, uint32_t half,
+                                                       uint32_t csub, uint32_t sub, uint32_t m, ulonglong2* kv,
+                                                       uint32_t* op, uint32_t cap) {
+  const uint64_t lt = (1ULL << (__lane_id() & 63u)) - 1;
+#pragma unroll
+  for (int u = 0; u < kPre; ++u) {
+    const bool match = pre_valid(a, pr, u, half, csub, sub);
+    const uint64_t bal = __ballot(match);
+    const uint32_t idx = m + (uint32_t)__popcll(bal & lt);
+    if (match && idx < cap) {
+      kv[idx] = make_ulonglong2(pr.k[u], pr.v[u]);
+      op[idx] = pr.op[u];
+    }
+    m += (uint32_t)__popcll(bal);
+  }
+  return m;
+}
+
+// Lane xs (< kPartSubs): the record count of the partition bucket's
+// sub-region xs.  The load is issued with the prefetch; sub_count_max, the
+// largest of them on every lane, waits for it.
+__device__ __forceinline__ uint32_t sub_count_load(const BucketArgs& a, uint32_t pb) {
+  const uint32_t lane = __lane_id() & 63u;
+  return lane < kPartSubs ? min(a.cursor[(lane << (a.p1 - a.sbb)) + pb], a.capx) : 0u;
+}
+__device__ __forceinline__ uint32_t sub_count_max(uint32_t csub) {
+  uint32_t cmax = csub;
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, o));
+  return (uint32_t)__shfl((int)cmax, 0);
+}
+
+// The split requests the pass stored (nreq, need: the wave's LDS words) go to
+// the bucket's grant shard.  Wave-uniform.
+__device__ __forceinline__ void request_tail(const BucketArgs& a, uint32_t w, const uint32_t& nreq,
+                                             const uint32_t& need, uint32_t db) {
+  __builtin_amdgcn_wave_barrier();
+  const uint32_t nr = min(nreq, kSplitCap);
+  if (nr) request_splits(a, w, nr, need > db ? need : 0u);
+}
+
+// The pass's counters into this bucket's own stat slots (no shared-line
+// atomics: one contended device atomic per wave costs more than the wave's
+// work).  wsv: the slots' values, lane k holding slot k, loaded at the start
+// of the pass.  The lean pass is the case of one round, no split, no growth.
+__device__ __forceinline__ void publish_stats(const BucketArgs& a, uint32_t w, uint64_t wsv, WaveStat c) {
+  const uint32_t lane = __lane_id() & 63u;
+  for (int o = 32; o > 0; o >>= 1) {
+    c.lines += (uint32_t)__shfl_down((int)c.lines, o);
+    c.waited += (uint32_t)__shfl_down((int)c.waited, o);
+  }
+  const uint32_t s0 = (uint32_t)__shfl((int)c.lines, 0), s1 = (uint32_t)__shfl((int)c.waited, 0);
+  const uint32_t s3 = (uint32_t)__shfl((int)c.loss, 0), s4 = (uint32_t)__shfl((int)c.runs, 0);
+  const uint32_t add = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? c.splits : lane == 3 ? s3
+                     : lane == 4 ? s4 : lane == 5 ? c.rounds : 0u;
+  uint64_t* ws = a.wstat + (size_t)w * kWStat;
+  if (lane < 6u && add) ws[lane] = wsv + add;
+  if (lane == 3u && s3) atomicAdd(&a.ctl->loss_events, 1u);  // never on the hot path: loss is rare
+  // slot 6: max rounds (low 16 bits) | max local depth (bits 16-23) | growths << 32
+  if (lane == 6u && (c.max_rounds || c.max_ld || c.grow)) {
+    const uint64_t mr = max((uint32_t)(wsv & 0xFFFF), c.max_rounds);
+    const uint64_t ml = max((uint32_t)((wsv >> 16) & 0xFF), c.max_ld);
+    ws[6] = mr | (ml << 16) | (((wsv >> 32) + c.grow) << 32);
+  }
+  if (lane == 0 && c.bad) atomicOr(&a.ctl->err, 4u);
+}
 
 
-// pre_m (final pass only): the chunk's pre_m ops are already in S.kv / S.op
-// (k_mixed_small); 0: the bucket's parked ops or its records
+// ------------------------------------------------- the phases of a bucket pass
+//
+// bucket_body below is the outline; each phase is a function of the wave's
+// LDS (BucketLds), the lane's registers (ChunkRegs, RoundOps) and the pass's
+// counters (WaveStat).  REG = !FINAL && !MIXED throughout: the insert-only
+// apply passes keep each op's {key, value, rop} in its owner lane's registers
+// (chunk slot j*64 + lane); their LDS holds only the keys.
+
+static_assert(kPre == kPer, "the prefetched records fill the chunk registers slot for slot");
+
+// REG: the chunk's ops in registers, slot j of lane l being chunk slot j*64 + l
+struct ChunkRegs {
+  uint64_t k[kPer], v[kPer];
+  uint32_t op[kPer];
+  bool ok[kPer];  // the slot holds an op
+};
+
+// A round's view of the lane's kPer chunk slots: which are pending, their key
+// and rop word, and what the lookup found
+struct RoundOps {
+  bool pq[kPer];
+  uint64_t kk[kPer];
+  uint32_t ro[kPer];
+  uint32_t e8[kPer], home8[kPer], x8[kPer];  // directory entry, home line, sub-directory index
+};
+
+// The chunk slot of a lane's j-th op: strided in the apply pass (a half-full
+// chunk leaves whole j-iterations idle, skipped; REG: where the registers
+// hold it), blocked for the 64-bit register sort of the other paths
+__device__ __forceinline__ uint32_t chunk_slot(bool strided, int j) {
+  const uint32_t lane = __lane_id() & 63u;
+  return strided ? (uint32_t)j * 64u + lane : kPer * lane + (uint32_t)j;
+}
+
+// Apply pass: a sub-directory of up to kLdsDir entries is read once into LDS
+// (alongside the record loads) instead of one dependent global load per op.
+// Loaded at the start of the pass, written to S.dir at first use: the loads
+// (which wait for the header) overlap the record loads' wait and the hashing.
+struct LdsDir {
+  bool on = false, written = false;
+  uint32_t v0 = 0, v1 = 0;  // entries lane and lane + 64
+};
+__device__ __forceinline__ LdsDir lds_dir_load(const BucketArgs& a, uint32_t off, uint32_t db) {
+  const uint32_t lane = __lane_id() & 63u;
+  LdsDir d;
+  d.on = (1u << db) <= kLdsDir;
+  if (d.on) {
+    if (lane < (1u << db)) d.v0 = ld_u32_l2(a.pool + off + lane);
+    if (lane + 64u < (1u << db)) d.v1 = ld_u32_l2(a.pool + off + lane + 64u);
+  }
+  return d;
+}
+
+// REG: every lane takes chunk slots j*64 + lane of the m ops in kv[] / op[]
+__device__ __forceinline__ void take_chunk(const ulonglong2* kv, const uint32_t* op, uint32_t m, ChunkRegs& r) {
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t i = (uint32_t)j * 64u + (__lane_id() & 63u);
+    r.ok[j] = i < m;
+    if (r.ok[j]) {
+      const ulonglong2 p = kv[i];
+      r.k[j] = p.x;
+      r.v[j] = p.y;
+      r.op[j] = op[i];
+    }
+  }
+}
+
+// ---- loading a chunk.  Four sources: the batch's records (first pass), the
+// bucket's parked list, a chunk the caller pre-loaded (nothing to do), and
+// the tile walk of a bucket with more ops than a chunk (big_chunk above).
+
+// First pass: the bucket's records of the batch into the chunk -- the
+// prefetched ones if they are all there is (at most 32 per sub-region, no
+// overflow), else collected.  Returns their number; past C nothing usable is
+// loaded (the final pass takes the bucket).
+template <bool REG, class Lds>
+__device__ __forceinline__ uint32_t load_records(const BucketArgs& a, Lds& S, uint32_t pb, uint32_t sub,
+                                                 const PreRecs& pr, uint32_t csub, uint32_t cmax, uint32_t novf,
+                                                 uint32_t C, ChunkRegs& r) {
+  const bool prefetched = cmax <= 32u && novf == 0;
+  uint32_t m = 0;
+  if constexpr (REG) {
+    if (prefetched) {
+      // the prefetched records stay where they were loaded: chunk slot
+      // u*64 + lane (sub-region u*2 + lane/32), holes where the record is
+      // another sub-bucket's or past the sub-region's count
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        r.ok[u] = pre_valid(a, pr, u, 0, csub, sub);
+        r.k[u] = pr.k[u];
+        r.v[u] = pr.v[u];
+        r.op[u] = pr.op[u];
+        m += (uint32_t)__popcll(__ballot(r.ok[u]));
+      }
+    } else {
+      // collect compacts into the (still unused) sort scratch and sort
+      // keys (contiguous: kCW pairs), the rop words into the key array,
+      // then every lane takes chunk slots j*64 + lane into registers
+      ulonglong2* stg = reinterpret_cast<ulonglong2*>(S.u);
+      uint32_t* sop = reinterpret_cast<uint32_t*>(S.key);
+      m = collect(a, pb, sub, csub, novf, stg, sop);
+      if (m <= C) take_chunk(stg, sop, m, r);
+      __builtin_amdgcn_wave_barrier();
+    }
+  } else {
+    if (prefetched) m = compact_prefetched(a, pr, 0, csub, sub, 0, S.kv, S.op, (uint32_t)kCW);
+    else m = collect(a, pb, sub, csub, novf, S.kv, S.op);
+  }
+  return m;
+}
+
+// A later pass: the m ops parked on the bucket's wait list
+template <bool REG, class Lds>
+__device__ __forceinline__ void load_parked(const ulonglong2* wl_kv, const uint32_t* wl_op, uint32_t m, Lds& S,
+                                            ChunkRegs& r) {
+  if constexpr (REG) {
+    take_chunk(wl_kv, wl_op, m, r);
+  } else {
+    for (uint32_t i = __lane_id() & 63u; i < m; i += 64) {
+      S.kv[i] = wl_kv[i];
+      S.op[i] = wl_op[i];
+    }
+  }
+}
+
+// every op of the loaded chunk is pending and has claimed nothing
+template <bool REG, class Lds>
+__device__ __forceinline__ void mark_pending(Lds& S, uint32_t m, const ChunkRegs& r) {
+  const uint32_t lane = __lane_id() & 63u;
+  if constexpr (REG) {
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const uint32_t i = (uint32_t)j * 64u + lane;
+      S.pend[i] = r.ok[j] ? 1 : 0;
+      S.pos[i] = 0xFFFF;
+      if (r.ok[j]) S.key[i] = r.k[j];
+    }
+  } else {
+    for (uint32_t i = lane; i < m; i += 64) {
+      S.pend[i] = 1;
+      S.pos[i] = 0xFFFF;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---- a round
+
+// The lane's ops still pending (o.pq, with key and rop word); returns how many
+template <bool REG, class Lds>
+__device__ __forceinline__ uint32_t gather_pending(const Lds& S, const ChunkRegs& r, uint32_t m, bool strided,
+                                                   RoundOps& o) {
+  uint32_t cntp = 0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t i = chunk_slot(strided, j);
+    if constexpr (REG) {
+      o.pq[j] = r.ok[j] && S.pend[i];
+      o.kk[j] = r.k[j];
+      o.ro[j] = r.op[j];
+    } else {
+      o.pq[j] = i < m && S.pend[i];
+      if (o.pq[j]) {
+        o.kk[j] = S.kv[i].x;
+        o.ro[j] = S.op[i];
+      }
+    }
+    cntp += o.pq[j];
+  }
+  return cntp;
+}
+
+// More rounds than the depth bound allows: cannot happen; the pending ops
+// fail loudly (CAPACITY, error flag 2) rather than spin
+template <class Lds>
+__device__ __forceinline__ void fail_pending(const BucketArgs& a, Lds& S, bool strided, const RoundOps& o) {
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (o.pq[j]) {
+      a.st[o.ro[j] & kOpMask] = 6;
+      S.pend[chunk_slot(strided, j)] = 0;
+    }
+  if ((__lane_id() & 63u) == 0) atomicOr(&a.ctl->err, 2u);
+}
+
+// Entry lookup: each pending op's home line, sub-directory index and
+// directory entry (from S.dir when the sub-directory is LDS-resident)
+template <bool FINAL, class Lds>
+__device__ __forceinline__ void lookup_entries(const BucketArgs& a, Lds& S, uint32_t off, uint32_t db, LdsDir& d,
+                                               RoundOps& o) {
+  const uint32_t lane = __lane_id() & 63u;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (o.pq[j]) {
+      const uint64_t h = hash64(o.kk[j]);
+      o.home8[j] = (uint32_t)(h & 0xFF);
+      o.x8[j] = sub_index(h, a.sbits, a.p1, db);
+    }
+  if constexpr (!FINAL) {
+    if (d.on && !d.written) {
+      if (lane < (1u << db)) S.dir[lane] = d.v0;
+      if (lane + 64u < (1u << db)) S.dir[lane + 64u] = d.v1;
+      __builtin_amdgcn_wave_barrier();
+      d.written = true;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (o.pq[j]) {
+      if constexpr (!FINAL) o.e8[j] = d.on ? S.dir[o.x8[j]] : ld_u32_l2(a.pool + off + o.x8[j]);
+      else o.e8[j] = ld_u32_l2(a.pool + off + o.x8[j]);
+    }
+}
+
+// The bin of an op on an LDS-resident sub-directory: its segment's first
+// sub-directory index (one bin per segment)
+__device__ __forceinline__ uint32_t first_sub_index(const BucketArgs& a, uint32_t db, uint32_t x, uint32_t e) {
+  return x & ~((1u << (db - (de_ld(e) - (a.sbits + a.p1)))) - 1u);
+}
+
+// Ordering on an LDS-resident sub-directory (apply passes), without a 64-bit
+// sort: the np pending ops in batch order (32-bit keys op << 8 | slot), then
+// a stable counting sort by bin (< kLdsDir).  Leaves the sort keys in S.sk
+// run by run, the run bounds in S.runq, the depths in S.L and -- unless the
+// sub-directory is wide (128 entries: two bins per lane, the runs load their
+// own bitmaps) -- the bitmap of each of the first kBmLanes runs in its row of
+// S.u.  Returns the number of runs.  srow: stamped if not null.
+template <class Lds>
+__device__ __forceinline__ uint32_t order_by_bins(const BucketArgs& a, Lds& S, const RoundOps& o, uint32_t np,
+                                                  uint32_t db, bool wide, uint64_t* srow) {
+  const uint32_t lane = __lane_id() & 63u;
+  uint32_t* hist = S.u;                                  // [128] ops per bin
+  uint32_t* cur = S.u + 128;                             // [128] next position of the bin
+  uint8_t* xcs = reinterpret_cast<uint8_t*>(S.u + 256);  // [kCW] bin of each slot
+  uint32_t* bseg = S.u + 256 + kCW / 4;                  // [128] segment of each bin
+  hist[lane] = 0;
+  hist[lane + 64] = 0;
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (o.pq[j]) {
+      const uint32_t i = (uint32_t)j * 64u + lane;
+      const uint32_t xc = first_sub_index(a, db, o.x8[j], o.e8[j]);
+      xcs[i] = (uint8_t)xc;
+      bseg[xc] = de_seg(o.e8[j]);
+      atomicAdd(&hist[xc], 1u);
+      S.sk[i] = sk_make(de_seg(o.e8[j]), o.ro[j] & kOpMask, i, o.home8[j]);  // by slot for now
+      S.L[i] = (uint8_t)(de_ld(o.e8[j]) | ((o.ro[j] & kGetBit) ? 0x80u : 0u));
+    }
+  __builtin_amdgcn_wave_barrier();
+  // each non-empty bin's lane fetches its segment's bitmap now; the
+  // loads land while the ops are sorted
+  const uint32_t hv = hist[lane], hv2 = wide ? hist[lane + 64] : 0u;
+  uint4 pbm[8];
+  if (hv && !wide) {
+    const uint32_t* og = a.occ + (size_t)bseg[lane] * 32u;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) pbm[jj] = ld_u4_l2(og + 4 * jj);
+  }
+  stamp(srow, kBsBinned, lane == 0);
+  // batch order without a comparison sort: k_part tiles are 4096
+  // consecutive ops, and a bucket holds ~0-2 ops per tile, so a
+  // counting sort by the op's tile bin (256 bins) leaves only tiny bins
+  // to order by op (insertion sort, one lane per bin)
+  uint32_t* th = S.u + 448;     // [256] per-bin counts, then offsets
+  uint32_t* o32 = S.u + 704;    // [kCW] keys (op << 8 | slot) in batch order
+  static_assert(704 + kCW <= kBmWords, "sort scratch");
+  {
+    const uint32_t lgn = 32u - (uint32_t)__builtin_clz((uint32_t)max<uint64_t>(a.n - 1, 1));
+    const uint32_t tsh = max(12u, lgn > 8u ? lgn - 8u : 0u);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) th[4 * lane + t] = 0;
+    __builtin_amdgcn_wave_barrier();
+    uint32_t tb[kPer], tr[kPer];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (o.pq[j]) {
+        tb[j] = min((o.ro[j] & kOpMask) >> tsh, 255u);
+        tr[j] = atomicAdd(&th[tb[j]], 1u);
+      }
+    __builtin_amdgcn_wave_barrier();
+    uint32_t c4[4], s4 = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      c4[t] = th[4 * lane + t];
+      s4 += c4[t];
+    }
+    uint32_t tot;
+    uint32_t ex = wave_excl_scan(s4, &tot);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      th[4 * lane + t] = ex;
+      ex += c4[t];
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < kPer; ++j)
+      if (o.pq[j]) o32[th[tb[j]] + tr[j]] = ((o.ro[j] & kOpMask) << 8) | ((uint32_t)j * 64u + lane);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (c4[t] < 2) continue;
+      const uint32_t b0 = th[4 * lane + t], b1 = b0 + c4[t];
+      for (uint32_t x = b0 + 1; x < b1; ++x) {  // insertion sort by (op, slot)
+        const uint32_t v = o32[x];
+        uint32_t y = x;
+        while (y > b0 && o32[y - 1] > v) {
+          o32[y] = o32[y - 1];
+          --y;
+        }
+        o32[y] = v;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  stamp(srow, kBsBatchOrder, lane == 0);
+  uint32_t rx, nruns;
+  {  // bins: exclusive offsets; the non-empty ones are the runs
+    uint32_t tot;
+    const uint32_t ex = wave_excl_scan(hv + hv2, &tot);  // bins lane, lane + 64 in turn
+    cur[lane] = ex;
+    cur[lane + 64] = ex + hv;
+    rx = wave_excl_scan((hv ? 1u : 0u) + (hv2 ? 1u : 0u), &nruns);
+    if (hv) S.runq[rx] = (uint16_t)ex;
+    if (hv2) S.runq[rx + (hv ? 1u : 0u)] = (uint16_t)(ex + hv);
+    if (lane == 0) S.runq[nruns] = (uint16_t)np;
+  }
+  __builtin_amdgcn_wave_barrier();
+  const uint64_t lt = (1ULL << lane) - 1;
+  uint64_t skv[kPer];
+  uint32_t dst[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {  // positions j*64 + lane, in batch order
+    const uint32_t q = (uint32_t)j * 64u + lane;
+    const bool valid = q < np;
+    const uint32_t i = valid ? (o32[q] & 0xFFu) : 0u;
+    const uint32_t v = valid ? xcs[i] : 0u;
+    uint64_t M = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+      if (b == 6 && !wide) break;
+      const bool bit = (v >> b) & 1u;
+      const uint64_t bb = __ballot(bit);
+      M &= bit ? bb : ~bb;
+    }
+    const uint32_t base = cur[v];
+    dst[j] = base + (uint32_t)__popcll(M & lt);
+    skv[j] = valid ? S.sk[i] : 0ULL;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && lane == 63u - (uint32_t)__builtin_clzll(M)) cur[v] = base + (uint32_t)__popcll(M);
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if ((uint32_t)j * 64u + lane < np) S.sk[dst[j]] = skv[j];
+  // run rx's bitmap row (the sort scratch above is dead now)
+  if (hv && !wide && rx < (uint32_t)kBmLanes) put_bitmap_row(S.u + rx * 33u, pbm);
+  __builtin_amdgcn_wave_barrier();
+  return nruns;
+}
+
+// Ordering by a 64-bit sort of (segment, batch index) keys (wave_sort8) and
+// run detection: the same outputs as order_by_bins but the bitmaps.  at: this
+// lane's first position among the np pending ops.
+template <class Lds>
+__device__ __forceinline__ uint32_t order_by_sort(Lds& S, const RoundOps& o, uint32_t at, uint32_t np, bool strided) {
+  const uint32_t lane = __lane_id() & 63u;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (o.pq[j]) {
+      const uint32_t i = chunk_slot(strided, j);
+      S.sk[at++] = sk_make(de_seg(o.e8[j]), o.ro[j] & kOpMask, i, o.home8[j]);
+      S.L[i] = (uint8_t)(de_ld(o.e8[j]) | ((o.ro[j] & kGetBit) ? 0x80u : 0u));
+    }
+  uint32_t p2 = 1;
+  while (p2 < np) p2 <<= 1;
+  __builtin_amdgcn_wave_barrier();
+  if (p2 > 1) wave_sort8(S.sk, p2, np);
+  // runs: maximal stretches with one segment
+  const uint32_t per_q = (np + 63) / 64;
+  uint32_t rc = 0, nruns;
+  for (uint32_t j = 0; j < per_q; ++j) {
+    const uint32_t q = lane * per_q + j;
+    if (q < np && (q == 0 || sk_seg(S.sk[q]) != sk_seg(S.sk[q - 1]))) ++rc;
+  }
+  uint32_t rat = wave_excl_scan(rc, &nruns);
+  for (uint32_t j = 0; j < per_q; ++j) {
+    const uint32_t q = lane * per_q + j;
+    if (q < np && (q == 0 || sk_seg(S.sk[q]) != sk_seg(S.sk[q - 1]))) S.runq[rat++] = (uint16_t)q;
+  }
+  if (lane == 0) S.runq[nruns] = (uint16_t)np;
+  return nruns;
+}
+
+// One lane per run, kBmLanes runs at a time, in batch order inside each run.
+// Insert-only batches only DECIDE slots here (S.pos); the pairs are written
+// by every lane afterwards.  Mixed batches store at once: a later Get of the
+// run must see them.  pre_bm: the first kBmLanes runs' bitmaps are in LDS.
+template <bool FINAL, bool MIXED>
+__device__ __forceinline__ void apply_runs(const RunCtx& rc, BucketLds<FINAL, !FINAL && !MIXED>& S, uint32_t nruns,
+                                           bool pre_bm, WaveStat& c) {
+  const uint32_t lane = __lane_id() & 63u;
+  for (uint32_t r0 = 0; r0 < nruns; r0 += kBmLanes) {
+    const uint32_t r = r0 + lane;
+    if (lane >= (uint32_t)kBmLanes || r >= nruns) continue;
+    const uint2 cw = apply_run<FINAL, MIXED>(rc, S, S.runq[r], S.runq[r + 1], pre_bm && r < (uint32_t)kBmLanes);
+    c.lines += cw.x;
+    c.waited += cw.y;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---- the claim write-outs
+
+// REG: each lane writes its own ops' claimed pairs from registers
+template <class Lds>
+__device__ __forceinline__ void store_claims_reg(const BucketArgs& a, Lds& S, const RoundOps& o, const ChunkRegs& r) {
+  const uint32_t lane = __lane_id() & 63u;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    if (!o.pq[j]) continue;
+    const uint32_t i = (uint32_t)j * 64u + lane;
+    const uint32_t pos = S.pos[i];
+    if (pos != 0xFFFFu) {
+      a.pairs[(size_t)de_seg(o.e8[j]) * kSlots + pos] = make_ulonglong2(r.k[j], r.v[j]);
+      S.pos[i] = 0xFFFF;
+      S.pend[i] = 0;  // (the fast claim loop leaves it set)
+    }
+  }
+}
+// Mixed apply passes: the claims the run loops left unstored (runs that never
+// reached the general loop), with their status
+template <class Lds>
+__device__ __forceinline__ void store_claims_mixed(const BucketArgs& a, Lds& S, uint32_t np) {
+  if (a.upsert) return;
+  for (uint32_t q = __lane_id() & 63u; q < np; q += 64) {
+    const uint64_t sk = S.sk[q];
+    const uint32_t i = sk_item(sk);
+    const uint32_t pos = S.pos[i];
+    if (pos != 0xFFFFu) {
+      a.pairs[(size_t)sk_seg(sk) * kSlots + pos] = S.kv[i];
+      a.st[sk_op(sk)] = 2;  // PMDFC_ST_INSERTED
+      S.pos[i] = 0xFFFF;
+    }
+  }
+}
+// Insert-only final pass: the claimed pairs from LDS, all lanes (loads first,
+// then stores)
+template <class Lds>
+__device__ __forceinline__ void store_claims_lds(const BucketArgs& a, Lds& S, uint32_t np) {
+  const uint32_t lane = __lane_id() & 63u;
+  for (uint32_t q0 = 0; q0 < np; q0 += 256) {
+    uint64_t kq[4], vq[4];
+    uint32_t aq[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint32_t q = q0 + u * 64 + lane;
+      aq[u] = 0xFFFFFFFFu;
+      if (q < np) {
+        const uint64_t sk = S.sk[q];
+        const uint32_t i = sk_item(sk);
+        const uint32_t pos = S.pos[i];
+        if (pos != 0xFFFFu) {
+          aq[u] = sk_seg(sk) * kSlots + pos;
+          const ulonglong2 kv = S.kv[i];
+          kq[u] = kv.x;
+          vq[u] = kv.y;
+          S.pos[i] = 0xFFFF;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (aq[u] != 0xFFFFFFFFu) a.pairs[aq[u]] = make_ulonglong2(kq[u], vq[u]);
+  }
+}
+
+// REG parking: the ops a full window left pending (S.pend 2) go to the
+// bucket's wait list, copied by their owner lanes
+template <class Lds>
+__device__ __forceinline__ void park_pending_reg(Lds& S, const RoundOps& o, const ChunkRegs& r, ulonglong2* wl_kv,
+                                                 uint32_t* wl_op) {
+  const uint32_t lane = __lane_id() & 63u;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t i = (uint32_t)j * 64u + lane;
+    if (o.pq[j] && S.pend[i] == 2) {
+      const uint32_t k = atomicAdd(&S.nsplit, 1u);
+      wl_kv[k] = make_ulonglong2(r.k[j], r.v[j]);
+      wl_op[k] = r.op[j];
+    }
+  }
+}
+
+// Final pass only: the round's ns queued splits, inline.  First the
+// sub-directory deepens if a child needs more bits (pool exhausted: the
+// blocked ops fail with CAPACITY and nothing splits), then each split moves
+// its entries (wave_split) and its directory half (dir_split).
+__device__ __forceinline__ void grow_and_split(const BucketArgs& a, uint32_t w, BucketLds<true, false>& S, uint32_t ns,
+                                               uint32_t& off, uint32_t& db, WaveStat& c, uint64_t* srow) {
+  const uint32_t lane = __lane_id() & 63u;
+  const uint32_t need = S.need;
+  if (need > db) {
+    const uint32_t size = 1u << need;
+    uint32_t no = 0;
+    const bool fx = a.pfix && need <= kFixedBits;  // grows in place in its fixed slot
+    if (lane == 0 && !fx) no = atomicAdd(&a.ctl->pool_cur, size);
+    no = fx ? w * kFixedSlot : (uint32_t)__shfl((int)no, 0);
+    if ((uint64_t)no + size > a.pool_cap) {
+      if (lane == 0) atomicOr(&a.ctl->err, 1u);
+      for (uint32_t s = lane; s < ns; s += 64) {
+        if (S.split[s] == ~0ULL) continue;
+        const uint32_t i = (uint32_t)S.split[s] & 0xFFFFu;
+        a.st[S.op[i] & kOpMask] = 6;
+        S.pend[i] = 0;
+      }
+      __builtin_amdgcn_wave_barrier();
+      return;
+    }
+    grow_subdir(a, w, no, need, off, db);
+    ++c.grow;
+  }
+  for (uint32_t s = 0; s < ns; ++s) {
+    const uint64_t e = S.split[s];
+    if (e == ~0ULL) continue;  // its child id ran out (CAPACITY)
+    const uint32_t i = (uint32_t)e & 0xFFFFu;
+    const uint32_t L = (uint32_t)(e >> 16) & 31u;
+    const uint32_t c1 = (uint32_t)(e >> 21);
+    const uint32_t x = sub_index(hash64(S.kv[i].x), a.sbits, a.p1, db);
+    const uint32_t seg = de_seg(ld_u32_l2(a.pool + off + x));
+    bool bad = false;
+    const uint32_t loss = wave_split(a.pairs, a.occ, a.ldep, seg, c1, L, S.u, &bad, nullptr, a.drops,
+                                     &a.ctl->drop_n, S.op[i] & kOpMask);
+    dir_split(a, off, db, x, seg, c1, L);
+    __builtin_amdgcn_s_waitcnt(0);
+    ++c.splits;
+    c.loss += loss;
+    c.bad += bad;
+    c.max_ld = max(c.max_ld, L + 1);
+  }
+  __builtin_amdgcn_wave_barrier();
+  stamp(srow, kBsFinSplit, lane == 0);
+}
+
+// One bucket pass of directory bucket w.
+// k_apply (FINAL = false, high occupancy, no split code): one round; a run
+// blocked by a full window requests a split and parks the rest of the run.
+// FIRST takes the bucket's records of the batch, else its parked ops (after
+// committing the last split round's splits).
+// The final pass (FINAL = true): buckets with parked ops, granted splits or
+// too many ops for one chunk; rounds with inline splits until its ops are
+// done.  pre_m: the chunk's pre_m ops are already in S.kv / S.op
+// (k_mixed_small); kBigBucket: walk the bucket's records (k_medium).
 // Returns 0 (a bucket that needs the final pass is listed in fin).
 template <bool FINAL, bool MIXED, bool FIRST>
 __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint32_t w,  // w: directory bucket
                                             BucketLds<FINAL, !FINAL && !MIXED>& S,  // the kernel's LDS
                                             uint32_t pre_m = 0) {
   static_assert(!(FINAL && FIRST), "the final pass is never the first");
-  // REG: the insert-only apply passes (k_apply / k_apply_parked) keep each
-  // op's {key, value, rop} in its owner lane's registers (chunk slot j*64 +
-  // lane); LDS holds only the keys.  3 KiB less LDS per wave: 4 waves per
-  // SIMD instead of 3.
   constexpr bool REG = !FINAL && !MIXED;
-  ulonglong2* const s_kv = S.kv;
-  uint64_t* const s_key = S.key;
-  uint32_t* const s_op = S.op;
-  uint64_t* const s_sk = S.sk;
-  uint16_t* const s_pos = S.pos;
-  uint16_t* const s_runq = S.runq;
-  uint8_t* const s_L = S.L;
-  uint8_t* const s_pend = S.pend;
-  uint64_t* const s_split = S.split;
-  uint32_t* const s_u = S.u;
-  uint32_t& s_nsplit = S.nsplit;
-  uint32_t& s_nreq = S.nreq;
-  uint32_t& s_need = S.need;
-
   const uint32_t lane = __lane_id() & 63u;  // (not threadIdx.x: callers may run several waves per workgroup)
   const uint32_t pb = w >> a.sbb, sub = w & ((1u << a.sbb) - 1);
-  constexpr bool first = FIRST;  // k_apply (mode 0): the batch's records; else parked ops
   uint32_t nw = 0;
-  if (!first) {
+  if (!FIRST) {
     nw = (FINAL && pre_m) ? pre_m : a.wl_n[w];
     if (nw == 0 && a.ngrant[w] == 0) return 0u;
     if (!FINAL && nw == kBigBucket) return 0u;  // the final pass takes it (listed by the first pass)
@@ -1876,34 +2574,16 @@ __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint3
   const bool big = FINAL && nw == kBigBucket;
   ulonglong2* const wl_kv = a.wl_kv + (size_t)w * kCW;
   uint32_t* const wl_op = a.wl_op + (size_t)w * kCW;
-  if (first) BK_STAMP(0);
-  if (FINAL) BK_STAMP(8);
-  if (first && a.mode == 0 && a.clear_next) {  // the next batch's cursors start at zero
-    if (sub == 0 && lane < kPartSubs) a.cursor_next[(lane << (a.p1 - a.sbb)) + pb] = 0;
-    if (w == 0 && lane == 0) *a.ovf_next = 0;
-  }
-  if (first && a.mode == 0 && w == 0) clear_other_parity(a);
+  uint64_t* const srow = bucket_stamp_row(a, w);
+  if (FIRST) stamp(srow, kBsStart, lane == 0);
+  if (FINAL) stamp(srow, kBsFinStart, lane == 0);
+  if (FIRST && a.mode == 0) first_pass_clears(a, w);
   // first pass: the first 32 records of each of the bucket's 8 sub-regions
   // and its stat slots are loaded before anything else is known (one round
   // trip with the header and cursor loads instead of three dependent ones)
-  constexpr int kPre = 4;  // 4 x 64 = 256 records
-  static_assert(kPre * 64 == 32 * kPartSubs, "prefetch: 32 records per sub-region");
-  uint32_t pr_op[kPre];
-  uint64_t pr_k[kPre], pr_v[kPre];
-  const uint64_t rb0 = (uint64_t)pb * a.cap;
-  // lane xs (< kPartSubs): sub-region xs's record count
-  const uint32_t csub = lane < kPartSubs ? min(a.cursor[(lane << (a.p1 - a.sbb)) + pb], a.capx) : 0u;
-  if (first) {
-#pragma unroll
-    for (int u = 0; u < kPre; ++u) {
-      const uint32_t jj = (uint32_t)u * 64u + lane;  // sub-region jj / 32, record jj % 32
-      const uint64_t j = rb0 + (uint64_t)(jj >> 5) * a.capx + min(jj & 31u, a.capx - 1u);
-      pr_op[u] = a.rop[j];
-      const ulonglong2 kv = a.rkv[j];
-      pr_k[u] = kv.x;
-      pr_v[u] = kv.y;
-    }
-  }
+  const uint32_t csub = sub_count_load(a, pb);
+  PreRecs pr;
+  if (FIRST) prefetch_records(a, pb, 0, pr);
   const uint64_t wsv = lane < 7u ? a.wstat[(size_t)w * kWStat + lane] : 0ULL;
   uint32_t off, db;
   {
@@ -1911,34 +2591,19 @@ __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint3
     off = hdr_off(hd);
     db = hdr_db(hd);
   }
-  uint32_t c_runs = 0, c_rounds = 0, c_waited = 0, c_lines = 0, c_splits = 0, c_loss = 0;
-  uint32_t c_grow = 0, c_maxr = 0, c_bad = 0, my_max_ld = 0;
-  if (!first) commit_splits(a, w, off, db, c_splits, c_grow, my_max_ld);
+  WaveStat c;
+  if (!FIRST) commit_splits(a, w, off, db, c);
   const uint32_t C = a.chunk;
   const uint32_t full = FINAL ? 0u : a.ctl->full;
-  // apply pass: a small sub-directory is read once into LDS (alongside the
-  // record loads) instead of one dependent global load per op
-  bool ldir = !FINAL && (1u << db) <= kLdsDir;
-  uint32_t dirv0 = 0, dirv1 = 0;
-  bool dirw = false;  // S.dir written
-  if constexpr (!FINAL) {
-    // loaded now, written to LDS at first use: the loads (which wait for the
-    // header) overlap the record loads' wait and the hashing
-    if (ldir) {
-      if (lane < (1u << db)) dirv0 = ld_u32_l2(a.pool + off + lane);
-      if (lane + 64u < (1u << db)) dirv1 = ld_u32_l2(a.pool + off + lane + 64u);
-    }
-  }
+  LdsDir ldir;
+  if constexpr (!FINAL) ldir = lds_dir_load(a, off, db);
   if (lane == 0) {
-    s_nsplit = 0;
-    s_nreq = 0;
-    s_need = db;
+    S.nsplit = 0;
+    S.nreq = 0;
+    S.need = db;
   }
   __builtin_amdgcn_wave_barrier();
-  uint32_t cmax = csub;  // the largest sub-region count (the prefetch covers 32 of each)
-#pragma unroll
-  for (int o = 4; o > 0; o >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, o));
-  cmax = (uint32_t)__shfl((int)cmax, 0);
+  const uint32_t cmax = sub_count_max(csub);  // (the prefetch covers 32 of each sub-region)
   const uint32_t novf = *a.ovf;
   const uint32_t ntile = (uint32_t)((a.n + kPartTile - 1) / kPartTile);
   BigLds* BL = nullptr;
@@ -1950,70 +2615,14 @@ __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint3
     }
   }
   bool first_chunk = true;
-  uint64_t rk[kPer], rv[kPer];  // REG: the ops of chunk slots j*64 + lane
-  uint32_t rop[kPer];
-  bool rok[kPer];
+  ChunkRegs r;
 #pragma unroll
-  for (int j = 0; j < kPer; ++j) rok[j] = false;
-  while (first || nw != 0) {
+  for (int j = 0; j < kPer; ++j) r.ok[j] = false;
+  while (FIRST || nw != 0) {
+    // ---- load the chunk
     uint32_t m = 0;
-    if (first) {
-      if (REG && cmax <= 32u && novf == 0) {
-        // the prefetched records stay where they were loaded: chunk slot
-        // u*64 + lane (sub-region u*2 + lane/32), holes where the record is
-        // another sub-bucket's or past the sub-region's count
-        const uint32_t sbm = (1u << a.sbb) - 1;
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const uint32_t jj = (uint32_t)u * 64u + lane;
-          const uint32_t cs = (uint32_t)__shfl((int)csub, (int)(jj >> 5));
-          rok[u] = (jj & 31u) < cs && ((pr_op[u] >> 22) & sbm) == sub;
-          rk[u] = pr_k[u];
-          rv[u] = pr_v[u];
-          rop[u] = pr_op[u];
-          m += (uint32_t)__popcll(__ballot(rok[u]));
-        }
-      } else if (REG) {
-        // collect compacts into the (still unused) sort scratch and sort
-        // keys (contiguous: kCW pairs), the rop words into the key array,
-        // then every lane takes chunk slots j*64 + lane into registers
-        ulonglong2* stg = reinterpret_cast<ulonglong2*>(s_u);
-        uint32_t* sop = reinterpret_cast<uint32_t*>(s_key);
-        m = collect(a, pb, sub, csub, novf, stg, sop);
-        if (m <= C) {
-#pragma unroll
-          for (int j = 0; j < kPer; ++j) {
-            const uint32_t i = (uint32_t)j * 64u + lane;
-            rok[j] = i < m;
-            if (rok[j]) {
-              const ulonglong2 kv = stg[i];
-              rk[j] = kv.x;
-              rv[j] = kv.y;
-              rop[j] = sop[i];
-            }
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      } else if (cmax <= 32u && novf == 0) {
-        const uint64_t lt = (1ULL << lane) - 1;
-        const uint32_t sbm = (1u << a.sbb) - 1;
-        m = 0;
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const uint32_t jj = (uint32_t)u * 64u + lane;
-          const uint32_t cs = (uint32_t)__shfl((int)csub, (int)(jj >> 5));
-          const bool match = (jj & 31u) < cs && ((pr_op[u] >> 22) & sbm) == sub;
-          const uint64_t bal = __ballot(match);
-          const uint32_t idx = m + (uint32_t)__popcll(bal & lt);
-          if (match && idx < (uint32_t)kCW) {
-            s_kv[idx] = make_ulonglong2(pr_k[u], pr_v[u]);
-            s_op[idx] = pr_op[u];
-          }
-          m += (uint32_t)__popcll(bal);
-        }
-      } else {
-        m = collect(a, pb, sub, csub, novf, s_kv, s_op);
-      }
+    if (FIRST) {
+      m = load_records<REG>(a, S, pb, sub, pr, csub, cmax, novf, C, r);
       if (m > C) {
         if (lane == 0) {
           a.wl_n[w] = kBigBucket;  // too many for one chunk: final pass
@@ -2023,490 +2632,96 @@ __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint3
       }
     } else if (!big) {
       m = nw;
-      if constexpr (REG) {
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          const uint32_t i = (uint32_t)j * 64u + lane;
-          rok[j] = i < m;
-          if (rok[j]) {
-            const ulonglong2 kv = wl_kv[i];
-            rk[j] = kv.x;
-            rv[j] = kv.y;
-            rop[j] = wl_op[i];
-          }
-        }
-      } else if (!(FINAL && pre_m)) {
-        for (uint32_t i = lane; i < m; i += 64) {
-          s_kv[i] = wl_kv[i];
-          s_op[i] = wl_op[i];
-        }
-      }
+      if (!(FINAL && pre_m)) load_parked<REG>(wl_kv, wl_op, m, S, r);
       __builtin_amdgcn_wave_barrier();
     } else {
-      if constexpr (FINAL) m = big_chunk(a, BL, pb, sub, ntile, C, bt, bmp, s_kv, s_op);
+      if constexpr (FINAL) m = big_chunk(a, BL, pb, sub, ntile, C, bt, bmp, S.kv, S.op);
       if (m == 0) break;
     }
-    if (first_chunk && (FINAL || first)) BK_STAMP(FINAL ? 9 : 1);
-    if constexpr (REG) {
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        const uint32_t i = (uint32_t)j * 64u + lane;
-        s_pend[i] = rok[j] ? 1 : 0;
-        s_pos[i] = 0xFFFF;
-        if (rok[j]) s_key[i] = rk[j];
-      }
-    } else {
-      for (uint32_t i = lane; i < m; i += 64) {
-        s_pend[i] = 1;
-        s_pos[i] = 0xFFFF;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    if (first_chunk && (FINAL || FIRST)) stamp(srow, FINAL ? kBsFinLoaded : kBsLoaded, lane == 0);
+    mark_pending<REG>(S, m, r);
     uint32_t rounds = 0;
-    // chunk slot of a lane's j-th op: strided in the apply pass (a half-full
-    // chunk leaves whole j-iterations idle, skipped; REG: where the registers
-    // hold it), blocked for the 64-bit register sort of the other paths
-    const bool strided = REG || (!FINAL && ldir);
+    const bool strided = REG || (!FINAL && ldir.on);
     for (uint32_t round = 0; m > 0; ++round) {
-      // ---- a. sort keys of the pending ops
-      uint64_t kk[kPer];
-      uint32_t ro[kPer];
-      bool pq[kPer];
-      uint32_t cntp = 0;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        const uint32_t i = strided ? (uint32_t)j * 64u + lane : kPer * lane + j;
-        if constexpr (REG) {
-          pq[j] = rok[j] && s_pend[i];
-          kk[j] = rk[j];
-          ro[j] = rop[j];
-        } else {
-          pq[j] = i < m && s_pend[i];
-          if (pq[j]) {
-            kk[j] = s_kv[i].x;
-            ro[j] = s_op[i];
-          }
-        }
-        cntp += pq[j];
-      }
+      uint64_t* const srow0 = (first_chunk && round == 0) ? srow : nullptr;  // round 0 of the first chunk is stamped
+      // ---- the pending ops and their directory entries
+      RoundOps o;
       uint32_t np;
-      uint32_t at = wave_excl_scan(cntp, &np);
+      const uint32_t at = wave_excl_scan(gather_pending<REG>(S, r, m, strided, o), &np);
       if (np == 0) break;
       if (round >= kRoundGuard) {
-        // cannot happen (depth is bounded); fail loudly rather than spin
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if (pq[j]) {
-            a.st[ro[j] & kOpMask] = 6;
-            s_pend[strided ? (uint32_t)j * 64u + lane : kPer * lane + j] = 0;
-          }
-        if (lane == 0) atomicOr(&a.ctl->err, 2u);
+        fail_pending(a, S, strided, o);
         break;
       }
       ++rounds;
-      uint32_t e8[kPer], home8[kPer], x8[kPer];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j)
-        if (pq[j]) {
-          const uint64_t h = hash64(kk[j]);
-          home8[j] = (uint32_t)(h & 0xFF);
-          x8[j] = sub_index(h, a.sbits, a.p1, db);
-        }
-      if constexpr (!FINAL) {
-        if (ldir && !dirw) {
-          if (lane < (1u << db)) S.dir[lane] = dirv0;
-          if (lane + 64u < (1u << db)) S.dir[lane + 64u] = dirv1;
-          __builtin_amdgcn_wave_barrier();
-          dirw = true;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kPer; ++j)
-        if (pq[j]) {
-          if constexpr (!FINAL) e8[j] = ldir ? S.dir[x8[j]] : ld_u32_l2(a.pool + off + x8[j]);
-          else e8[j] = ld_u32_l2(a.pool + off + x8[j]);
-        }
+      lookup_entries<FINAL>(a, S, off, db, ldir, o);
       if constexpr (REG) {
         // insert-only passes on a sub-directory of <= 32 entries: claims in
         // parallel (fast_claim); false = a segment with too many interacting
         // ops, nothing done yet: the sorted run loop below takes the round
         if ((1u << db) <= kFastBins && !a.upsert) {
-          const uint32_t lbase = a.sbits + a.p1;
-          // bin: the segment's first sub-index (< 32)
-          const auto bin = [&](int j) -> uint32_t { return x8[j] & ~((1u << (db - (de_ld(e8[j]) - lbase))) - 1u); };
-          if (fast_claim<kCW, kFastBins>(a, w, s_u, s_key, wl_kv, wl_op, &s_nsplit, &s_nreq, &s_need, rk, rv, rop, pq, e8,
-                                         home8, x8, bin, c_runs, c_lines, c_waited,
-                              (first && first_chunk && a.stamps) ? a.stamps + (size_t)w * 16 : nullptr))
+          const auto bin = [&](int j) -> uint32_t { return first_sub_index(a, db, o.x8[j], o.e8[j]); };
+          if (fast_claim<kCW, kFastBins>(a, w, S.u, S.key, wl_kv, wl_op, &S.nsplit, &S.nreq, &S.need,
+                                         LaneOps{r.k, r.v, r.op, o.pq, o.e8, o.home8, o.x8}, bin, c,
+                                         FIRST ? srow0 : nullptr))
             break;  // (an apply pass is one round)
         }
       }
-      uint32_t nruns;
-      // a 128-entry sub-directory (large tables): two bins per lane, and the
-      // runs load their own bitmaps
+      // ---- order them into runs, one per segment, each in batch order
       const bool wide = db > 6;
-      const bool pre_bm = !FINAL && ldir && !wide;
-      if (!FINAL && ldir) {
-        // ---- segment runs without a 64-bit sort: the ops in batch order
-        // (32-bit keys op << 8 | slot), then a stable counting sort by the
-        // segment's first sub-directory index (< kLdsDir bins)
-        uint32_t* hist = s_u;                                  // [128] ops per bin
-        uint32_t* cur = s_u + 128;                             // [128] next position of the bin
-        uint8_t* xcs = reinterpret_cast<uint8_t*>(s_u + 256);  // [kCW] bin of each slot
-        uint32_t* bseg = s_u + 256 + kCW / 4;                  // [128] segment of each bin
-        hist[lane] = 0;
-        hist[lane + 64] = 0;
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t lbase = a.sbits + a.p1;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if (pq[j]) {
-            const uint32_t i = (uint32_t)j * 64u + lane;
-            const uint32_t L = de_ld(e8[j]);
-            const uint32_t xc = x8[j] & ~((1u << (db - (L - lbase))) - 1u);
-            xcs[i] = (uint8_t)xc;
-            bseg[xc] = de_seg(e8[j]);
-            atomicAdd(&hist[xc], 1u);
-            s_sk[i] = sk_make(de_seg(e8[j]), ro[j] & kOpMask, i, home8[j]);  // by slot for now
-            s_L[i] = (uint8_t)(L | ((ro[j] & kGetBit) ? 0x80u : 0u));
-          }
-        uint32_t p2 = 1;
-        while (p2 < np) p2 <<= 1;
-        __builtin_amdgcn_wave_barrier();
-        // each non-empty bin's lane fetches its segment's bitmap now; the
-        // loads land while the ops are sorted
-        const uint32_t hv = hist[lane], hv2 = wide ? hist[lane + 64] : 0u;
-        uint4 pbm[8];
-        if (hv && !wide) {
-          const uint32_t* og = a.occ + (size_t)bseg[lane] * 32u;
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) pbm[jj] = ld_u4_l2(og + 4 * jj);
-        }
-        if (first_chunk && round == 0 && first) BK_STAMP(4);
-        // batch order without a comparison sort: k_part tiles are 4096
-        // consecutive ops, and a bucket holds ~0-2 ops per tile, so a
-        // counting sort by the op's tile bin (256 bins) leaves only tiny bins
-        // to order by op (insertion sort, one lane per bin)
-        uint32_t* th = s_u + 448;     // [256] per-bin counts, then offsets
-        uint32_t* o32 = s_u + 704;    // [kCW] keys (op << 8 | slot) in batch order
-        static_assert(704 + kCW <= kBmWords, "sort scratch");
-        {
-          const uint32_t lgn = 32u - (uint32_t)__builtin_clz((uint32_t)max<uint64_t>(a.n - 1, 1));
-          const uint32_t tsh = max(12u, lgn > 8u ? lgn - 8u : 0u);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) th[4 * lane + t] = 0;
-          __builtin_amdgcn_wave_barrier();
-          uint32_t tb[kPer], tr[kPer];
-#pragma unroll
-          for (int j = 0; j < kPer; ++j)
-            if (pq[j]) {
-              tb[j] = min((ro[j] & kOpMask) >> tsh, 255u);
-              tr[j] = atomicAdd(&th[tb[j]], 1u);
-            }
-          __builtin_amdgcn_wave_barrier();
-          uint32_t c4[4], s4 = 0;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            c4[t] = th[4 * lane + t];
-            s4 += c4[t];
-          }
-          uint32_t tot;
-          uint32_t ex = wave_excl_scan(s4, &tot);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            th[4 * lane + t] = ex;
-            ex += c4[t];
-          }
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int j = 0; j < kPer; ++j)
-            if (pq[j]) o32[th[tb[j]] + tr[j]] = ((ro[j] & kOpMask) << 8) | ((uint32_t)j * 64u + lane);
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if (c4[t] < 2) continue;
-            const uint32_t b0 = th[4 * lane + t], b1 = b0 + c4[t];
-            for (uint32_t x = b0 + 1; x < b1; ++x) {  // insertion sort by (op, slot)
-              const uint32_t v = o32[x];
-              uint32_t y = x;
-              while (y > b0 && o32[y - 1] > v) {
-                o32[y] = o32[y - 1];
-                --y;
-              }
-              o32[y] = v;
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-        if (first_chunk && round == 0 && first) BK_STAMP(5);
-        uint32_t rx;
-        {  // bins: exclusive offsets; the non-empty ones are the runs
-          uint32_t tot;
-          const uint32_t ex = wave_excl_scan(hv + hv2, &tot);  // bins lane, lane + 64 in turn
-          cur[lane] = ex;
-          cur[lane + 64] = ex + hv;
-          rx = wave_excl_scan((hv ? 1u : 0u) + (hv2 ? 1u : 0u), &nruns);
-          if (hv) s_runq[rx] = (uint16_t)ex;
-          if (hv2) s_runq[rx + (hv ? 1u : 0u)] = (uint16_t)(ex + hv);
-          if (lane == 0) s_runq[nruns] = (uint16_t)np;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const uint64_t lt = (1ULL << lane) - 1;
-        uint64_t skv[kPer];
-        uint32_t dst[kPer];
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {  // positions j*64 + lane, in batch order
-          const uint32_t q = (uint32_t)j * 64u + lane;
-          const bool valid = q < np;
-          const uint32_t i = valid ? (o32[q] & 0xFFu) : 0u;
-          const uint32_t v = valid ? xcs[i] : 0u;
-          uint64_t M = __ballot(valid);
-#pragma unroll
-          for (int b = 0; b < 7; ++b) {
-            if (b == 6 && !wide) break;
-            const bool bit = (v >> b) & 1u;
-            const uint64_t bb = __ballot(bit);
-            M &= bit ? bb : ~bb;
-          }
-          const uint32_t base = cur[v];
-          dst[j] = base + (uint32_t)__popcll(M & lt);
-          skv[j] = valid ? s_sk[i] : 0ULL;
-          __builtin_amdgcn_wave_barrier();
-          if (valid && lane == 63u - (uint32_t)__builtin_clzll(M)) cur[v] = base + (uint32_t)__popcll(M);
-          __builtin_amdgcn_wave_barrier();
-        }
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if ((uint32_t)j * 64u + lane < np) s_sk[dst[j]] = skv[j];
-        // run rx's bitmap row (the sort scratch above is dead now)
-        if (hv && !wide && rx < (uint32_t)kBmLanes) {
-          uint32_t* row = s_u + rx * 33u;
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) {
-            row[4 * jj] = pbm[jj].x;
-            row[4 * jj + 1] = pbm[jj].y;
-            row[4 * jj + 2] = pbm[jj].z;
-            row[4 * jj + 3] = pbm[jj].w;
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      } else {
-#pragma unroll
-        for (int j = 0; j < kPer; ++j)
-          if (pq[j]) {
-            const uint32_t i = strided ? (uint32_t)j * 64u + lane : kPer * lane + j;
-            s_sk[at++] = sk_make(de_seg(e8[j]), ro[j] & kOpMask, i, home8[j]);
-            s_L[i] = (uint8_t)(de_ld(e8[j]) | ((ro[j] & kGetBit) ? 0x80u : 0u));
-          }
-        uint32_t p2 = 1;
-        while (p2 < np) p2 <<= 1;
-        __builtin_amdgcn_wave_barrier();
-        if (p2 > 1) wave_sort8(s_sk, p2, np);
-        // ---- runs: maximal stretches with one segment
-        const uint32_t per_q = (np + 63) / 64;
-        uint32_t rc = 0;
-        for (uint32_t j = 0; j < per_q; ++j) {
-          const uint32_t q = lane * per_q + j;
-          if (q < np && (q == 0 || sk_seg(s_sk[q]) != sk_seg(s_sk[q - 1]))) ++rc;
-        }
-        uint32_t rat = wave_excl_scan(rc, &nruns);
-        for (uint32_t j = 0; j < per_q; ++j) {
-          const uint32_t q = lane * per_q + j;
-          if (q < np && (q == 0 || sk_seg(s_sk[q]) != sk_seg(s_sk[q - 1]))) s_runq[rat++] = (uint16_t)q;
-        }
-        if (lane == 0) s_runq[nruns] = (uint16_t)np;
-      }
+      uint32_t nruns;
+      if (!FINAL && ldir.on) nruns = order_by_bins(a, S, o, np, db, wide, FIRST ? srow0 : nullptr);
+      else nruns = order_by_sort(S, o, at, np, strided);
       if (lane == 0 && FINAL) {
-        s_nsplit = 0;
-        s_need = db;
+        S.nsplit = 0;
+        S.need = db;
       }
       __builtin_amdgcn_wave_barrier();
-      if (first_chunk && round == 0 && (FINAL || first)) BK_STAMP(FINAL ? 10 : 2);
-      c_runs += lane == 0 ? nruns : 0;
-      // ---- b. one lane per run, in batch order.  Insert-only batches only
-      // DECIDE slots here (s_pos); the pairs are written by every lane below.
-      // Mixed batches store at once: a later Get of the run must see them.
-      {
-        uint32_t* bm = s_u + (lane % kBmLanes) * 33u;
-        const RunCtx rc{a.pairs, a.occ, a.vout, a.st, a.ctl, a.req + (size_t)w * kSplitCap,
-                        a.reqop + (size_t)w * kSplitCap, a.mixed, a.max_segments, full, (uint32_t)(!FINAL && a.mode == 2),
-                        (!FINAL && first && a.stamps) ? a.stamps + (size_t)w * 16 : nullptr,
-                        a.sbits, a.p1, db, a.upsert, (first && a.upsert) ? a.upos : nullptr};
-        for (uint32_t r0 = 0; r0 < nruns; r0 += kBmLanes) {
-          const uint32_t r = r0 + lane;
-          if (lane >= (uint32_t)kBmLanes || r >= nruns) continue;
-          const uint2 cw = apply_run<FINAL, MIXED>(rc, s_sk, s_runq[r], s_runq[r + 1], s_L, s_kv, s_key, s_op, s_pos,
-                                            s_pend, s_split, &s_nsplit, &s_nreq, &s_need, bm, wl_kv, wl_op,
-                                            pre_bm && r < (uint32_t)kBmLanes);
-          c_lines += cw.x;
-          c_waited += cw.y;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (first_chunk && round == 0 && !FINAL && first) BK_STAMP(6);
-      if constexpr (REG) {
-        // ---- b'. each lane writes its own ops' claimed pairs from registers
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          if (!pq[j]) continue;
-          const uint32_t i = (uint32_t)j * 64u + lane;
-          const uint32_t pos = s_pos[i];
-          if (pos != 0xFFFFu) {
-            a.pairs[(size_t)de_seg(e8[j]) * kSlots + pos] = make_ulonglong2(rk[j], rv[j]);
-            s_pos[i] = 0xFFFF;
-            s_pend[i] = 0;  // (the fast claim loop leaves it set)
-          }
-        }
-      } else if (MIXED && !FINAL) {
-        // ---- b'. mixed apply passes: the claims the run loops left unstored
-        // (runs that never reached the general loop), with their status
-        if (!a.upsert) {
-          for (uint32_t q = lane; q < np; q += 64) {
-            const uint64_t sk = s_sk[q];
-            const uint32_t i = sk_item(sk);
-            const uint32_t pos = s_pos[i];
-            if (pos != 0xFFFFu) {
-              a.pairs[(size_t)sk_seg(sk) * kSlots + pos] = s_kv[i];
-              a.st[sk_op(sk)] = 2;  // PMDFC_ST_INSERTED
-              s_pos[i] = 0xFFFF;
-            }
-          }
-        }
-      } else if (!MIXED) {
-        // ---- b'. write the claimed pairs, all lanes (loads first, then stores)
-        for (uint32_t q0 = 0; q0 < np; q0 += 256) {
-          uint64_t kq[4], vq[4];
-          uint32_t aq[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const uint32_t q = q0 + u * 64 + lane;
-            aq[u] = 0xFFFFFFFFu;
-            if (q < np) {
-              const uint64_t sk = s_sk[q];
-              const uint32_t i = sk_item(sk);
-              const uint32_t pos = s_pos[i];
-              if (pos != 0xFFFFu) {
-                aq[u] = sk_seg(sk) * kSlots + pos;
-                const ulonglong2 kv = s_kv[i];
-                kq[u] = kv.x;
-                vq[u] = kv.y;
-                s_pos[i] = 0xFFFF;
-              }
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (aq[u] != 0xFFFFFFFFu) a.pairs[aq[u]] = make_ulonglong2(kq[u], vq[u]);
-        }
-      }
+      if (FINAL || FIRST) stamp(srow0, FINAL ? kBsFinOrdered : kBsOrdered, lane == 0);
+      c.runs += lane == 0 ? nruns : 0;
+      // ---- apply the runs
+      const RunCtx rc{a.pairs, a.occ, a.vout, a.st, a.ctl, a.req + (size_t)w * kSplitCap,
+                      a.reqop + (size_t)w * kSplitCap, a.mixed, a.max_segments, full, (uint32_t)(!FINAL && a.mode == 2),
+                      (!FINAL && FIRST) ? srow : nullptr,
+                      a.sbits, a.p1, db, a.upsert, (FIRST && a.upsert) ? a.upos : nullptr, wl_kv, wl_op};
+      apply_runs<FINAL, MIXED>(rc, S, nruns, !FINAL && ldir.on && !wide, c);
+      if (!FINAL && FIRST) stamp(srow0, kBsRunsDone, lane == 0);
+      // ---- write the claims
+      if constexpr (REG) store_claims_reg(a, S, o, r);
+      else if constexpr (MIXED && !FINAL) store_claims_mixed(a, S, np);
+      else if constexpr (!MIXED) store_claims_lds(a, S, np);
       if (FINAL) __builtin_amdgcn_s_waitcnt(0);  // the next round re-reads the segments
       __builtin_amdgcn_wave_barrier();
-      if (first_chunk && round == 0 && (FINAL || first)) BK_STAMP(FINAL ? 11 : 3);
-      if constexpr (REG) {
-        // ---- e. park the ops a full window left pending (s_pend 2): their
-        // owner lanes copy them to the bucket's wait list
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          const uint32_t i = (uint32_t)j * 64u + lane;
-          if (pq[j] && s_pend[i] == 2) {
-            const uint32_t k = atomicAdd(&s_nsplit, 1u);
-            wl_kv[k] = make_ulonglong2(rk[j], rv[j]);
-            wl_op[k] = rop[j];
-          }
-        }
+      if (FINAL || FIRST) stamp(srow0, FINAL ? kBsFinWritten : kBsWritten, lane == 0);
+      // ---- park (apply passes: one round; parked ops wait for the split round)
+      if constexpr (REG) park_pending_reg(S, o, r, wl_kv, wl_op);
+      if constexpr (!FINAL) {
+        break;
+      } else {
+        // ---- grow and split inline, then the next round
+        const uint32_t ns = min(S.nsplit, kSplitCap);
+        if (ns == 0) continue;  // every pending op resolved (or failed) this round
+        grow_and_split(a, w, S, ns, off, db, c, srow0);
       }
-      if (!FINAL) break;  // k_apply: one round; parked ops wait for the split round
-      const uint32_t ns = min(s_nsplit, kSplitCap);
-      if (ns == 0) continue;  // every pending op resolved (or failed) this round
-      // ---- c. deepen the sub-directory if a child needs more bits
-      const uint32_t need = s_need;
-      if (need > db) {
-        const uint32_t size = 1u << need;
-        uint32_t no = 0;
-        const bool fx = a.pfix && need <= kFixedBits;  // grows in place in its fixed slot
-        if (lane == 0 && !fx) no = atomicAdd(&a.ctl->pool_cur, size);
-        no = fx ? w * kFixedSlot : (uint32_t)__shfl((int)no, 0);
-        if ((uint64_t)no + size > a.pool_cap) {
-          // sub-directory pool exhausted: the blocked ops fail (CAPACITY)
-          if (lane == 0) atomicOr(&a.ctl->err, 1u);
-          for (uint32_t s = lane; s < ns; s += 64) {
-            if (s_split[s] == ~0ULL) continue;
-            const uint32_t i = (uint32_t)s_split[s] & 0xFFFFu;
-            a.st[s_op[i] & kOpMask] = 6;
-            s_pend[i] = 0;
-          }
-          __builtin_amdgcn_wave_barrier();
-          continue;
-        }
-        grow_subdir(a, w, no, need, off, db);
-        ++c_grow;
-      }
-      // ---- d. splits
-      for (uint32_t s = 0; s < ns; ++s) {
-        const uint64_t e = s_split[s];
-        if (e == ~0ULL) continue;  // its child id ran out (CAPACITY)
-        const uint32_t i = (uint32_t)e & 0xFFFFu;
-        const uint32_t L = (uint32_t)(e >> 16) & 31u;
-        const uint32_t c1 = (uint32_t)(e >> 21);
-        const uint32_t x = sub_index(hash64(s_kv[i].x), a.sbits, a.p1, db);
-        const uint32_t seg = de_seg(ld_u32_l2(a.pool + off + x));
-        bool bad = false;
-        uint32_t loss = 0;
-        if constexpr (FINAL)
-          loss = wave_split(a.pairs, a.occ, a.ldep, seg, c1, L, s_u, &bad, nullptr, a.drops, &a.ctl->drop_n,
-                            s_op[i] & kOpMask);
-        dir_split(a, off, db, x, seg, c1, L);
-        __builtin_amdgcn_s_waitcnt(0);
-        ++c_splits;
-        c_loss += loss;
-        c_bad += bad;
-        my_max_ld = max(my_max_ld, L + 1);
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (first_chunk && round == 0) BK_STAMP(12);
     }
-    c_rounds += rounds;
-    c_maxr = max(c_maxr, rounds);
+    c.rounds += rounds;
+    c.max_rounds = max(c.max_rounds, rounds);
     first_chunk = false;
     if (!big) break;  // one chunk
   }
-  uint32_t to_final = 0;
+  // ---- publish: the wait list, the final-pass list, split requests, stats
   if (!FINAL) {
     // the last parked-op pass requests nothing: what it parks is the final pass's
-    to_final = (a.mode == 2 && s_nsplit) ? 1u : 0u;
+    const uint32_t to_final = (a.mode == 2 && S.nsplit) ? 1u : 0u;
     if (lane == 0) {
-      a.wl_n[w] = s_nsplit;  // parked ops (0: done)
+      a.wl_n[w] = S.nsplit;  // parked ops (0: done)
       if (to_final) a.fin[(a.par << a.p1) + atomicAdd(&a.ctl->nfin[a.par], 1u)] = w;
     }
+    request_tail(a, w, S.nreq, S.need, db);
   }
-  if (!FINAL) {
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t nr = min(s_nreq, kSplitCap);
-    if (nr) request_splits(a, w, nr, s_need > db ? s_need : 0u);
-  }
-  // ---- counters: this bucket's own stat slot (no shared-line atomics: one
-  // contended device atomic per wave costs more than the wave's work)
-  for (int o = 32; o > 0; o >>= 1) {
-    c_lines += (uint32_t)__shfl_down((int)c_lines, o);
-    c_waited += (uint32_t)__shfl_down((int)c_waited, o);
-  }
-  {  // slot k by lane k, from the values prefetched at the start
-    const uint32_t s0 = (uint32_t)__shfl((int)c_lines, 0), s1 = (uint32_t)__shfl((int)c_waited, 0);
-    const uint32_t s3 = (uint32_t)__shfl((int)c_loss, 0), s4 = (uint32_t)__shfl((int)c_runs, 0);
-    const uint32_t add = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? c_splits : lane == 3 ? s3
-                       : lane == 4 ? s4 : lane == 5 ? c_rounds : 0u;
-    uint64_t* ws = a.wstat + (size_t)w * kWStat;
-    if (lane < 6u && add) ws[lane] = wsv + add;
-    if (lane == 3u && s3) atomicAdd(&a.ctl->loss_events, 1u);  // never on the hot path: loss is rare
-    // slot 6: max rounds (low 16 bits) | max local depth (bits 16-23) | growths << 32
-    if (lane == 6u && (c_maxr || my_max_ld || c_grow)) {
-      const uint64_t mr = max((uint32_t)(wsv & 0xFFFF), c_maxr);
-      const uint64_t ml = max((uint32_t)((wsv >> 16) & 0xFF), my_max_ld);
-      ws[6] = mr | (ml << 16) | (((wsv >> 32) + c_grow) << 32);
-    }
-    if (lane == 0 && c_bad) atomicOr(&a.ctl->err, 4u);
-  }
-  if (first) BK_STAMP(7);
-  if (FINAL) BK_STAMP(13);
+  publish_stats(a, w, wsv, c);
+  if (FIRST) stamp(srow, kBsEnd, lane == 0);
+  if (FINAL) stamp(srow, kBsFinEnd, lane == 0);
   return 0;
 }
 
@@ -3091,7 +3306,7 @@ __global__ __launch_bounds__(64 * kSplitWaves, 2) void k_split(SplitArgs a) {
     if (!ok) continue;  // (uniform over a team: one k)
     bool b = false;
     uint64_t* stp = a.stamps && k < kSplitStamps ? a.stamps + (size_t)k * 8 : nullptr;
-    if (stp && lane == 0 && (!team || wv == 0)) stp[5] = wall_clock64();
+    stamp(stp, kSsStart, lane == 0 && (!team || wv == 0));
     const uint32_t trig = a.drops ? a.reqop[(size_t)w * kSplitCap + i] : 0u;
     const uint32_t ps = el.x & ((1u << 27) - 1), pl = el.x >> 27;
     if (team) {
@@ -3216,6 +3431,95 @@ struct CpLds {
 };
 static_assert(sizeof(CpLds) <= 40 * 1024, "4 workgroups of 8 waves per CU");
 
+// The wide lean pass's bins: bn[j], the first sub-index (< 128) of insert j's
+// segment, becomes the rank of that segment among those the bucket's inserts
+// touch (seen: 4 LDS words, zeroed).  False: more than nb segments.
+__device__ __forceinline__ bool dense_bins(uint32_t* seen, const bool (&pq)[kPer], uint32_t (&bn)[kPer], uint32_t nb) {
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (pq[j]) atomicOr(&seen[bn[j] >> 5], 1u << (bn[j] & 31u));
+  __builtin_amdgcn_wave_barrier();
+  const uint32_t s0 = seen[0], s1 = seen[1], s2 = seen[2], s3 = seen[3];
+  if (__builtin_popcount(s0) + __builtin_popcount(s1) + __builtin_popcount(s2) + __builtin_popcount(s3) > (int)nb)
+    return false;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t x = bn[j], q = x >> 5, below = (1u << (x & 31u)) - 1u;
+    uint32_t r = __builtin_popcount((q == 0 ? s0 : q == 1 ? s1 : q == 2 ? s2 : s3) & below);
+    r += q > 0 ? __builtin_popcount(s0) : 0;
+    r += q > 1 ? __builtin_popcount(s1) : 0;
+    r += q > 2 ? __builtin_popcount(s2) : 0;
+    bn[j] = r;
+  }
+  return true;
+}
+
+// The lean pass in last-writer-wins mode: each insert's window is probed for
+// its key over the occupied prefix (a stored key lies before the window's
+// first free slot: nothing is deleted).  upd[j]: the slot of insert j's key
+// (0xFFFF: absent); occw[2j], occw[2j + 1]: its window's occupancy words, for
+// fast_claim.  False: two inserts of one key, nothing probed (the general
+// pass takes the bucket).
+__device__ __forceinline__ bool upsert_probe(const BucketArgs& a, const bool (&pq)[kPer], const uint64_t (&rk)[kPer],
+                                             const uint32_t (&e8)[kPer], const uint32_t (&home8)[kPer],
+                                             uint32_t (&upd)[kPer], uint32_t (&occw)[2 * kPer]) {
+  const uint32_t lane = __lane_id() & 63u;
+  // two inserts of one key: the general pass (equal keys have equal hashes;
+  // a 32-bit hash collision only sends the bucket there too)
+  uint32_t hv[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) hv[q] = q < kPer && pq[q] ? (uint32_t)hash64(rk[q]) : 0xFFFFFFFFu;
+  wave_sort32<4>(hv, 256);
+  bool dup = false;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) dup |= hv[q] != 0xFFFFFFFFu && hv[q] == hv[q + 1];
+  const uint32_t nx = (uint32_t)__shfl_down((int)hv[0], 1);
+  dup |= lane < 63u && hv[3] != 0xFFFFFFFFu && hv[3] == nx;
+  if (__ballot(dup)) return false;
+  // the window's occupancy words, then its occupied prefix, line by line
+  // (the loads of all of a lane's inserts in flight together)
+  uint32_t nl[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    upd[j] = 0xFFFFu;
+    occw[2 * j] = occw[2 * j + 1] = 0;
+    if (!pq[j]) continue;
+    const uint32_t* og = a.occ + (size_t)de_seg(e8[j]) * 32u;
+    const uint32_t wi = home8[j] >> 3;
+    occw[2 * j] = ld_u32_l2(og + wi);
+    occw[2 * j + 1] = ld_u32_l2(og + ((wi + 1u) & 31u));
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const uint32_t win = __builtin_amdgcn_alignbit(occw[2 * j + 1], occw[2 * j], (home8[j] * 4u) & 31u);
+    const uint32_t ff = ~win ? (uint32_t)__builtin_ctz(~win) : 32u;  // first free slot of the window
+    nl[j] = pq[j] ? (ff + 3u) >> 2 : 0u;
+  }
+  for (uint32_t t = 0;; ++t) {
+    bool more = false;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) more |= t < nl[j] && upd[j] == 0xFFFFu;
+    if (!__ballot(more)) break;
+    uint64_t kq[kPer][4];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      if (t >= nl[j] || upd[j] != 0xFFFFu) continue;
+      const ulonglong2* ln = a.pairs + (size_t)de_seg(e8[j]) * kSlots + ((home8[j] + t) & 255u) * 4u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) kq[j][q] = reinterpret_cast<const uint64_t*>(ln + q)[0];
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      if (t >= nl[j] || upd[j] != 0xFFFFu) continue;
+#pragma unroll
+      for (int q = 3; q >= 0; --q)
+        if (kq[j][q] == rk[j]) upd[j] = ((home8[j] + t) * 4u + (uint32_t)q) & (kSlots - 1);
+    }
+  }
+  return true;
+}
+
 template <bool WIDE, bool UPS = false, bool CP = false>
 __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE>& S, uint32_t w,
                                                CpLds* cpl = nullptr) {
@@ -3223,45 +3527,31 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
   static_assert(!CP || (!WIDE && !UPS), "the coarse-partition pass is the lean insert-only one");
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t pb = w >> a.sbb, sub = w & ((1u << a.sbb) - 1);
-  uint64_t* const stamp = a.stamps ? a.stamps + (size_t)w * 16 : nullptr;
-#define FS_STAMP(ph) \
-  if (stamp && lane == 0) stamp[ph] = wall_clock64()
-  FS_STAMP(0);
-  if (a.clear_next) {  // the next batch's cursors start at zero
-    if (sub == 0 && lane < kPartSubs) a.cursor_next[(lane << (a.p1 - a.sbb)) + pb] = 0;
-    if (w == 0 && lane == 0) *a.ovf_next = 0;
-  }
-  if (w == 0) clear_other_parity(a);
+  uint64_t* const srow = bucket_stamp_row(a, w);
+  stamp(srow, kBsStart, lane == 0);
+  first_pass_clears(a, w);
   // one round trip: the first 32 records of each sub-region, the counts, the
   // header, the stat slots, the overflow count and the fixed sub-directory slot
-  uint32_t pr_op[4];
-  uint64_t pr_k[4], pr_v[4];
-  const uint64_t rb0 = (uint64_t)pb * a.cap;
+  PreRecs pr;
   constexpr int kCpLd = (int)(kPartSubs * kCpPre / (64 * kCpWaves));  // staging loads per thread
+  static_assert(kCpLd <= kPre, "the staging loads use the prefetch registers");
   if constexpr (CP) {
     // the workgroup stages kCpPre records of each sub-region (slot t of the
     // workgroup: sub-region t / kCpPre); a wave's loads land below
+    const uint64_t rb0 = (uint64_t)pb * a.cap;
 #pragma unroll
     for (int u = 0; u < kCpLd; ++u) {
       const uint32_t t = (uint32_t)u * 64u * kCpWaves + threadIdx.x;
       const uint64_t j = rb0 + (uint64_t)(t / kCpPre) * a.capx + min(t % kCpPre, a.capx - 1u);
-      pr_op[u] = a.rop[j];
+      pr.op[u] = a.rop[j];
       const ulonglong2 kv = a.rkv[j];
-      pr_k[u] = kv.x;
-      pr_v[u] = kv.y;
+      pr.k[u] = kv.x;
+      pr.v[u] = kv.y;
     }
   } else {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const uint32_t jj = (uint32_t)u * 64u + lane;  // sub-region jj / 32, record jj % 32
-    const uint64_t j = rb0 + (uint64_t)(jj >> 5) * a.capx + min(jj & 31u, a.capx - 1u);
-    pr_op[u] = a.rop[j];
-    const ulonglong2 kv = a.rkv[j];
-    pr_k[u] = kv.x;
-    pr_v[u] = kv.y;
+    prefetch_records(a, pb, 0, pr);
   }
-  }
-  const uint32_t csub = lane < kPartSubs ? min(a.cursor[(lane << (a.p1 - a.sbb)) + pb], a.capx) : 0u;
+  const uint32_t csub = sub_count_load(a, pb);
   const uint64_t wsv = lane < 7u ? a.wstat[(size_t)w * kWStat + lane] : 0ULL;
   const uint32_t* fslot = a.pool + (size_t)w * kFixedSlot;
   const uint32_t spec0 = (a.pfix && (WIDE || lane < 32u)) ? ld_u32_l2(fslot + lane) : 0u;
@@ -3279,10 +3569,7 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
     dv0 = (db <= C::MaxDb && lane < (1u << db)) ? ld_u32_l2(a.pool + off + lane) : 0u;
     if (WIDE) dv1 = (db <= C::MaxDb && lane + 64u < (1u << db)) ? ld_u32_l2(a.pool + off + 64u + lane) : 0u;
   }
-  uint32_t cmax = csub;
-#pragma unroll
-  for (int o = 4; o > 0; o >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, o));
-  cmax = (uint32_t)__shfl((int)cmax, 0);
+  const uint32_t cmax = sub_count_max(csub);
   bool pq[kPer];
   uint64_t rk[kPer], rv[kPer];
   uint32_t rop[kPer];
@@ -3293,8 +3580,8 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
 #pragma unroll
     for (int u = 0; u < kCpLd; ++u) {
       const uint32_t t = (uint32_t)u * 64u * kCpWaves + threadIdx.x;
-      cpl->st.op[t] = pr_op[u];
-      cpl->st.kv[t] = make_ulonglong2(pr_k[u], pr_v[u]);
+      cpl->st.op[t] = pr.op[u];
+      cpl->st.kv[t] = make_ulonglong2(pr.k[u], pr.v[u]);
     }
     __syncthreads();
     uint32_t dec = (db > C::MaxDb || novf != 0) ? 2u : cmax > kCpPre ? 2u : 0u;
@@ -3334,59 +3621,35 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
     __syncthreads();  // (the staging is dead: the waves' claim scratch overlays it)
     if (dec) return dec;
   } else {
-  if (db > C::MaxDb || novf != 0) return 2u;
-  if (cmax > C::FC) return 1u;
-  // compact the bucket's records into insert slots j * 64 + lane, j < FP
-  // (in sub-region order: records 0-31 of every sub-region, then 32-63 of
-  // those with more, ... -- k_part's sub-regions are ~Poisson(16) at config 2,
-  // so ~10 buckets a batch take the second load; a batch of fewer than
-  // kPartSubs partition tiles fills fewer sub-regions, more deeply.  The order
-  // of the slots does not matter, the claims are decided by op index)
-  const uint32_t sbm = (1u << a.sbb) - 1;
-  const uint64_t lt = (1ULL << lane) - 1;
-  uint32_t m = 0;
-  for (uint32_t half = 0; half * 32u < cmax; ++half) {
-    if (half) {
+    if (db > C::MaxDb || novf != 0) return 2u;
+    if (cmax > C::FC) return 1u;
+    // compact the bucket's records into insert slots j * 64 + lane, j < FP
+    // (in sub-region order: records 0-31 of every sub-region, then 32-63 of
+    // those with more, ... -- k_part's sub-regions are ~Poisson(16) at config 2,
+    // so ~10 buckets a batch take the second load; a batch of fewer than
+    // kPartSubs partition tiles fills fewer sub-regions, more deeply.  The order
+    // of the slots does not matter, the claims are decided by op index)
+    uint32_t m = 0;
+    for (uint32_t half = 0; half * 32u < cmax; ++half) {
+      if (half) prefetch_records(a, pb, half, pr);
+      m = compact_prefetched(a, pr, half, csub, sub, m, S.stage.kv, S.stage.op, C::FC);
+    }
+    if (m > C::FC) return 1u;
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t jj = (uint32_t)u * 64u + lane;
-        const uint64_t j = rb0 + (uint64_t)(jj >> 5) * a.capx + min(half * 32u + (jj & 31u), a.capx - 1u);
-        pr_op[u] = a.rop[j];
-        const ulonglong2 kv = a.rkv[j];
-        pr_k[u] = kv.x;
-        pr_v[u] = kv.y;
+    for (int j = 0; j < kPer; ++j) {
+      const uint32_t i = (uint32_t)j * 64u + lane;
+      pq[j] = j < C::FP && i < m;
+      rk[j] = rv[j] = 0;
+      rop[j] = 0;
+      if (pq[j]) {
+        const ulonglong2 kv = S.stage.kv[i];
+        rk[j] = kv.x;
+        rv[j] = kv.y;
+        rop[j] = S.stage.op[i];
       }
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const uint32_t jj = (uint32_t)u * 64u + lane;
-      const uint32_t cs = (uint32_t)__shfl((int)csub, (int)(jj >> 5));
-      const bool match = half * 32u + (jj & 31u) < cs && ((pr_op[u] >> 22) & sbm) == sub;
-      const uint64_t bal = __ballot(match);
-      const uint32_t idx = m + (uint32_t)__popcll(bal & lt);
-      if (match && idx < C::FC) {
-        S.stage.kv[idx] = make_ulonglong2(pr_k[u], pr_v[u]);
-        S.stage.op[idx] = pr_op[u];
-      }
-      m += (uint32_t)__popcll(bal);
-    }
-  }
-  if (m > C::FC) return 1u;
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    const uint32_t i = (uint32_t)j * 64u + lane;
-    pq[j] = j < C::FP && i < m;
-    rk[j] = rv[j] = 0;
-    rop[j] = 0;
-    if (pq[j]) {
-      const ulonglong2 kv = S.stage.kv[i];
-      rk[j] = kv.x;
-      rv[j] = kv.y;
-      rop[j] = S.stage.op[i];
-    }
-  }
-  __builtin_amdgcn_wave_barrier();  // (staging is dead: the claims' scratch overlays it)
+    __builtin_amdgcn_wave_barrier();  // (staging is dead: the claims' scratch overlays it)
   }
   if (lane == 0) {
     S.nsplit = 0;
@@ -3396,7 +3659,6 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
   if (WIDE && lane < 4) S.seen[lane] = 0;
   uint32_t e8[kPer], home8[kPer], x8[kPer], bn[WIDE ? kPer : 1];
   (void)bn;
-  const uint32_t lbase = a.sbits + a.p1;
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     home8[j] = x8[j] = 0;
@@ -3416,114 +3678,31 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
   }
   // bin: the segment's first sub-index; WIDE: the touched segments numbered
   // densely in sub-index order
-  const auto first_sub = [&](int j) -> uint32_t { return x8[j] & ~((1u << (db - (de_ld(e8[j]) - lbase))) - 1u); };
+  const auto first_sub = [&](int j) -> uint32_t { return first_sub_index(a, db, x8[j], e8[j]); };
   if constexpr (WIDE) {
 #pragma unroll
     for (int j = 0; j < kPer; ++j) bn[j] = pq[j] ? first_sub(j) : 0u;
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int j = 0; j < kPer; ++j)
-      if (pq[j]) atomicOr(&S.seen[bn[j] >> 5], 1u << (bn[j] & 31u));
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t s0 = S.seen[0], s1 = S.seen[1], s2 = S.seen[2], s3 = S.seen[3];
-    if (__builtin_popcount(s0) + __builtin_popcount(s1) + __builtin_popcount(s2) + __builtin_popcount(s3) > (int)C::NB)
-      return 1u;  // (nothing written yet)
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const uint32_t x = bn[j], q = x >> 5, below = (1u << (x & 31u)) - 1u;
-      uint32_t r = __builtin_popcount((q == 0 ? s0 : q == 1 ? s1 : q == 2 ? s2 : s3) & below);
-      r += q > 0 ? __builtin_popcount(s0) : 0;
-      r += q > 1 ? __builtin_popcount(s1) : 0;
-      r += q > 2 ? __builtin_popcount(s2) : 0;
-      bn[j] = r;
-    }
+    if (!dense_bins(S.seen, pq, bn, C::NB)) return 1u;  // (nothing written yet)
   }
   uint32_t upd[UPS ? kPer : 1], occw[UPS ? 2 * kPer : 1];
   if constexpr (UPS) {
-    // two inserts of one key: the general pass (equal keys have equal hashes;
-    // a 32-bit hash collision only sends the bucket there too)
-    uint32_t hv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) hv[q] = q < kPer && pq[q] ? (uint32_t)hash64(rk[q]) : 0xFFFFFFFFu;
-    wave_sort32<4>(hv, 256);
-    bool dup = false;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) dup |= hv[q] != 0xFFFFFFFFu && hv[q] == hv[q + 1];
-    const uint32_t nx = (uint32_t)__shfl_down((int)hv[0], 1);
-    dup |= lane < 63u && hv[3] != 0xFFFFFFFFu && hv[3] == nx;
-    if (__ballot(dup)) return 1u;
-    // the window's occupancy words, then its occupied prefix, line by line
-    // (the loads of all of a lane's inserts in flight together)
-    uint32_t nl[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      upd[j] = 0xFFFFu;
-      occw[2 * j] = occw[2 * j + 1] = 0;
-      if (!pq[j]) continue;
-      const uint32_t* og = a.occ + (size_t)de_seg(e8[j]) * 32u;
-      const uint32_t wi = home8[j] >> 3;
-      occw[2 * j] = ld_u32_l2(og + wi);
-      occw[2 * j + 1] = ld_u32_l2(og + ((wi + 1u) & 31u));
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const uint32_t win = __builtin_amdgcn_alignbit(occw[2 * j + 1], occw[2 * j], (home8[j] * 4u) & 31u);
-      const uint32_t ff = ~win ? (uint32_t)__builtin_ctz(~win) : 32u;  // first free slot of the window
-      nl[j] = pq[j] ? (ff + 3u) >> 2 : 0u;
-    }
-    for (uint32_t t = 0;; ++t) {
-      bool more = false;
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) more |= t < nl[j] && upd[j] == 0xFFFFu;
-      if (!__ballot(more)) break;
-      uint64_t kq[kPer][4];
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        if (t >= nl[j] || upd[j] != 0xFFFFu) continue;
-        const ulonglong2* ln = a.pairs + (size_t)de_seg(e8[j]) * kSlots + ((home8[j] + t) & 255u) * 4u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kq[j][q] = reinterpret_cast<const uint64_t*>(ln + q)[0];
-      }
-#pragma unroll
-      for (int j = 0; j < kPer; ++j) {
-        if (t >= nl[j] || upd[j] != 0xFFFFu) continue;
-#pragma unroll
-        for (int q = 3; q >= 0; --q)
-          if (kq[j][q] == rk[j]) upd[j] = ((home8[j] + t) * 4u + (uint32_t)q) & (kSlots - 1);
-      }
-    }
+    if (!upsert_probe(a, pq, rk, e8, home8, upd, occw)) return 1u;  // two inserts of one key
   }
-  FS_STAMP(1);
-  uint32_t c_runs = 0, c_lines = 0, c_waited = 0;
+  stamp(srow, kBsLoaded, lane == 0);
+  WaveStat c;
   const auto bin = [&](int j) -> uint32_t {
     if constexpr (WIDE) return bn[j];
     else return first_sub(j);
   };
   if (!fast_claim<C::FC, C::NB, UPS>(a, w, S.sc, nullptr, a.wl_kv + (size_t)w * kCW, a.wl_op + (size_t)w * kCW,
-                                     &S.nsplit, &S.nreq, &S.need, rk, rv, rop, pq, e8, home8, x8, bin, c_runs, c_lines,
-                                     c_waited, stamp, UPS ? upd : nullptr, UPS ? occw : nullptr))
+                                     &S.nsplit, &S.nreq, &S.need, LaneOps{rk, rv, rop, pq, e8, home8, x8}, bin, c, srow,
+                                     UPS ? upd : nullptr, UPS ? occw : nullptr))
     return 1u;
   if (lane == 0) a.wl_n[w] = S.nsplit;  // parked inserts (0: done)
-  {
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t nr = min(S.nreq, kSplitCap);
-    if (nr) request_splits(a, w, nr, S.need > db ? S.need : 0u);
-  }
-  // this bucket's stat slots, as bucket_body's first pass keeps them
-  for (int o = 32; o > 0; o >>= 1) {
-    c_lines += (uint32_t)__shfl_down((int)c_lines, o);
-    c_waited += (uint32_t)__shfl_down((int)c_waited, o);
-  }
-  {
-    const uint32_t s0 = (uint32_t)__shfl((int)c_lines, 0), s1 = (uint32_t)__shfl((int)c_waited, 0);
-    const uint32_t s4 = (uint32_t)__shfl((int)c_runs, 0);
-    const uint32_t add = lane == 0 ? s0 : lane == 1 ? s1 : lane == 4 ? s4 : lane == 5 ? 1u : 0u;
-    uint64_t* ws = a.wstat + (size_t)w * kWStat;
-    if (lane < 6u && add) ws[lane] = wsv + add;
-    if (lane == 6u) ws[6] = max((uint32_t)(wsv & 0xFFFF), 1u) | (((wsv >> 16) & 0xFF) << 16) | ((wsv >> 32) << 32);
-  }
-  FS_STAMP(7);
-#undef FS_STAMP
+  request_tail(a, w, S.nreq, S.need, db);
+  c.rounds = c.max_rounds = 1;
+  publish_stats(a, w, wsv, c);
+  stamp(srow, kBsEnd, lane == 0);
   return 0u;
 }
 

@@ -1086,3 +1086,124 @@ def test_debug_stamps_follow_the_batch(monkeypatch):
     assert np.all(bk2[:, 0] > bk[:, 0])
     assert t.stats()["error_flags"] == 0
     t.close()
+
+
+# One insert-only stream per first-pass variant, each in a child process (the
+# engine reads PMDFC_CP / PMDFC_FAST_APPLY once per process): 40 batches of
+# 20,000 fresh keys into CCEH_hybrid(8), so the table ramps through every
+# bucket resolution (splits and sub-directory growth in every batch) up to
+# its full 2^9 buckets (max_batch 65,536), where a 20,000-op batch is
+# eligible for the coarse partition and the default takes k_apply_fast_cp.
+_FIRST_PASS_CHILD = r'''
+import json, sys, numpy as np
+from oracle import oracle as O
+from pmdfc_amd.workload import uniform_keys
+import pmdfc_amd as P
+B, nb = 20000, 40
+t = P.CCEH(8, max_batch=1 << 16, max_segments=4096)
+o = O.OracleCCEH(t.initial_depth)
+ok = True
+for i in range(nb):
+    k = uniform_keys(810, i * B, B)
+    ok = ok and bool(np.array_equal(t.Insert(k, k ^ np.uint64(9)), o.insert(k, k ^ np.uint64(9))))
+d, od = t.dump(), o.dump()
+ok = ok and d["depth"] == od["depth"] and all(np.array_equal(d[f], od[f]) for f in ("local_depth", "keys", "values"))
+s, os_ = t.stats(), o.stats()
+print(json.dumps({"ok": ok, "stats": {k: int(v) for k, v in s.items()},
+                  "oracle": {"segments": o.num_segments, "depth": o.depth, "splits": int(os_["splits"]),
+                             "split_loss": int(os_["split_loss"])}}))
+t.close()
+'''
+_FIRST_PASS_ENVS = {"default": {}, "cp0": {"PMDFC_CP": "0"}, "fast_apply0": {"PMDFC_FAST_APPLY": "0"}}
+
+
+def test_first_pass_variants_keep_the_same_books():
+    """The lean first pass with the coarse partition (default), with the fine
+    one (PMDFC_CP=0) and the general first pass (PMDFC_FAST_APPLY=0) share
+    their prologue and their stat epilogue: each leaves the oracle's table and
+    the same path-independent stats (those the oracle keeps equal the
+    oracle's; "doublings" counts sub-directory growths, which the reference's
+    single directory does not have, so it is compared between the variants
+    only).  The path-dependent counters are printed, not compared."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    procs = {}
+    for name, env in _FIRST_PASS_ENVS.items():
+        e = dict(os.environ)
+        for k in ("PMDFC_CP", "PMDFC_FAST_APPLY", "PMDFC_CHUNK", "PMDFC_P1MAX"):
+            e.pop(k, None)
+        e.update(env)
+        procs[name] = subprocess.Popen([sys.executable, "-c", _FIRST_PASS_CHILD], cwd=repo, env=e,
+                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    res = {}
+    for name, p in procs.items():
+        out, err = p.communicate(timeout=600)
+        assert p.returncode == 0, (name, err[-2000:])
+        res[name] = json.loads(out.strip().splitlines()[-1])
+    for name, r in res.items():
+        print(name, {k: r["stats"][k] for k in ("insert_lines", "segment_runs", "insert_passes", "deferred_ops",
+                                                "max_rounds", "fast_declined")})
+    same = ("segments", "depth", "splits", "doublings", "split_loss", "batches", "error_flags", "bucket_bits")
+    ref = res["default"]
+    assert ref["stats"]["bucket_bits"] == 9, ref["stats"]  # at full resolution: the last batches took the coarse partition
+    for name, r in res.items():
+        assert r["ok"], name  # every status and the final table equal the oracle's
+        assert r["stats"]["error_flags"] == 0, name
+        assert r["stats"]["splits"] > 200, (name, r["stats"])  # the stream did split and grow
+        assert r["stats"]["doublings"] > 0, (name, r["stats"])
+        for k in same:
+            assert r["stats"][k] == ref["stats"][k], (name, k, r["stats"][k], ref["stats"][k])
+        for k, v in r["oracle"].items():
+            assert r["stats"][k] == v, (name, k, r["stats"][k], v)
+
+
+def test_every_chunk_loader_on_one_table(monkeypatch):
+    """Every way a bucket pass loads its chunk, on one small table with
+    64-op chunks (PMDFC_CHUNK, read at create): a 20,000-op insert batch whose
+    buckets overflow their chunk (the final pass's tile walk: whole tiles and
+    the in-tile map), mixed and insert batches that park ops behind splits
+    (the parked lists of the parked and the final pass), an 8,192-op batch
+    (k_medium: pre-marked big buckets) and a 200-op mixed batch (k_mixed_small:
+    the chunk loaded by the caller).  Every status and value after each batch
+    and the final table equal the serial oracle."""
+    monkeypatch.setenv("PMDFC_CHUNK", "64")
+    monkeypatch.delenv("PMDFC_P1MAX", raising=False)
+    rng = np.random.default_rng(31)
+    t = P.CCEH(depth=5, max_batch=20000, max_segments=4096)
+    o = O.OracleCCEH(5)
+    steps = [("insert", 20000), ("mixed", 12000), ("insert", 12000), ("insert", 20000), ("mixed", 20000),
+             ("insert", 9000), ("insert", 8192), ("mixed", 8192), ("mixed", 200), ("insert", 256)]
+    fresh = 0
+    stored = np.zeros(0, np.uint64)
+    for step, (kind, n) in enumerate(steps):
+        k = uniform_keys(811, fresh, n)
+        fresh += n
+        s0 = t.stats()["splits"]
+        if kind == "mixed":
+            ops = (rng.random(n) < 0.6).astype(np.uint8)
+            g = ops == 0
+            k[g] = np.where(rng.random(int(g.sum())) < 0.8, stored[rng.integers(0, stored.size, int(g.sum()))], k[g])
+            v = k ^ np.uint64(3)
+            out, st = t.Mixed(ops, k, v)
+            oout, ost = o.mixed(ops, k, v)
+            assert np.array_equal(out, oout), step
+            stored = np.concatenate([stored, k[ops == 1]])
+        else:
+            v = k ^ np.uint64(3)
+            st = t.Insert(k, v)
+            ost = o.insert(k, v)
+            stored = np.concatenate([stored, k])
+        assert np.array_equal(st, ost), step
+        print(step, kind, n, "splits", t.stats()["splits"] - s0)
+    v, st = t.Get(stored)
+    ov, ost = o.get(stored)
+    assert np.array_equal(st, ost) and np.array_equal(v, ov)
+    s = t.stats()
+    assert s["error_flags"] == 0
+    # (the stored keys need at least size / 1024 segments, each past the first 32 made by a split)
+    assert s["splits"] == o.stats()["splits"] and s["splits"] >= -(-stored.size // 1024) - 32
+    d, od = t.dump(), o.dump()
+    assert d["depth"] == od["depth"] and np.array_equal(d["local_depth"], od["local_depth"])
+    assert np.array_equal(d["keys"], od["keys"]) and np.array_equal(d["values"], od["values"])
+    t.close()
