@@ -85,6 +85,42 @@ def gen_cceh(upsert=False):
         json.dump(table, f, indent=1, sort_keys=True)
 
 
+def gen_split_shapes():
+    """The crafted split images of scenarios.split_shapes through the
+    reference's CCEH_hybrid.cpp: the summary of gen_cceh plus the entries the
+    splits dropped (inserted minus occupied: the streams insert no key twice)
+    and the Get result at EVERY Get position -- the dropped keys are what the
+    streams are for: get_hits_hex has one bit per Get in stream order (MSB
+    first), a hit's value is the one the stream inserted with that key
+    (checked here), and get_values_sha covers the whole result array
+    (scenarios.split_shape_get_values rebuilds it)."""
+    table = {}
+    for name, (init_cap, conv, ops, keys, vals) in S.split_shapes(O.hash64).items():
+        n = keys.size
+        payload = (np.array([init_cap, n], np.uint64).tobytes() + keys.astype("<u8").tobytes()
+                   + vals.astype("<u8").tobytes() + ops.astype(np.uint8).tobytes())
+        out = run("cceh", "ref_driver", payload)
+        p = 0
+        depth, nseg = np.frombuffer(out, "<u8", 2, p); p += 16
+        meta = np.frombuffer(out, "<u8", 2 * int(nseg), p).reshape(-1, 2); p += 16 * int(nseg)
+        skeys = np.frombuffer(out, "<u8", int(nseg) * 1024, p); p += 8 * int(nseg) * 1024
+        svals = np.frombuffer(out, "<u8", int(nseg) * 1024, p); p += 8 * int(nseg) * 1024
+        gv = np.frombuffer(out, "<u8", n, p); p += 8 * n
+        util = float(np.frombuffer(out, "<f8", 1, p)[0]); p += 8
+        cap = int(np.frombuffer(out, "<u8", 1, p)[0]); p += 8
+        assert p == len(out)
+        rec = S.summarize(depth, meta[:, 0], meta[:, 1], skeys, svals, gv, ops)
+        gets = ops == S.OP_GET
+        rec.update(init_cap=int(init_cap), convention=conv, n_ops=int(n), utilization=util, capacity=cap,
+                   split_loss=int((~gets).sum()) - rec["occupied"], n_gets=int(gets.sum()),
+                   get_hits_hex=np.packbits(gv[gets] != 0).tobytes().hex())
+        assert np.array_equal(S.split_shape_get_values(rec, ops, keys, vals), gv[gets])
+        table[name] = rec
+        print(name, "depth", int(depth), "nseg", int(nseg), "hits", rec["get_hits"], "dropped", rec["split_loss"])
+    with open(os.path.join(HERE, "split_shapes.json"), "w") as f:
+        json.dump(table, f, indent=1, sort_keys=True)
+
+
 def cbf_payload(k, m, ins, qs, dels):
     parts = [np.array([k, m, ins.size], np.uint64), ins, np.array([qs.size], np.uint64), qs,
              np.array([dels.size], np.uint64), dels]
@@ -255,9 +291,12 @@ def main():
         return gen_cceh()
     if sys.argv[1:] == ["upsert"]:
         return gen_cceh(upsert=True)
+    if sys.argv[1:] == ["split_shapes"]:
+        return gen_split_shapes()
     gen_hash()
     gen_cceh()
     gen_cceh(upsert=True)
+    gen_split_shapes()
     gen_bloom()
     gen_cbfseq()
     gen_replay()

@@ -121,9 +121,208 @@ def _find_keys(seed, hash64, want_low, want_top2, count):
     return np.array(out[:count], dtype=np.uint64)
 
 
+def _key_cells(hash64, prefix, pbits, seed=900, n=1 << 21):
+    """Pick keys by home line, segment prefix and child bit: the keys of
+    uniform_keys(seed, 0, n) whose top `pbits` hash bits equal `prefix` (they
+    live in the segment of local depth L = pbits with that prefix), sorted
+    into cells by home line h & 0xFF and by the bit that chooses the child
+    when that segment splits, hash bit 63 - L.  The pool is filtered once;
+    returns a factory of take(line, child, count) functions, each of which
+    hands out a cell's keys in pool order, every key once."""
+    ks = uniform_keys(seed, 0, n)
+    h = hash64(ks)
+    sel = (h >> np.uint64(64 - pbits)) == np.uint64(prefix)
+    ks, h = ks[sel], h[sel]
+    cell = ((h & np.uint64(0xFF)) | (((h >> np.uint64(63 - pbits)) & np.uint64(1)) << np.uint64(8))).astype(np.int64)
+    order = np.argsort(cell, kind="stable")
+    ks = ks[order]
+    start = np.searchsorted(cell[order], np.arange(513))
+
+    def taker():
+        used = np.zeros(512, np.int64)
+
+        def take(line, child, count=1):
+            c = int(line) | (int(child) << 8)
+            a = int(start[c] + used[c])
+            if a + count > int(start[c + 1]):
+                raise ValueError(f"key pool too small for line {line}, child {child}")
+            used[c] += count
+            return ks[a:a + count]
+        return take
+    return taker
+
+
+# Crafted split images (split_shapes).  An insert of home line h takes the
+# first free slot of [4h, 4h + 32) mod 1024, so a list of (home line, child
+# bit, count) groups in insert order fixes the segment image exactly.  Each
+# entry: the image groups, the trigger's (line, child), and what the shape
+# guard of test_oracle_golden.py checks before the trigger -- the occupied
+# slots and the clusters (maximal occupied runs, (first slot, length), the run
+# through slot 1023 continued at slot 0).
+def _per_line(lines, child, count=4):
+    return [(h, child(h) if callable(child) else child, count) for h in lines]
+
+
+def _cyclic_heads_image():
+    """A cyclic parent on the cluster path.  Lines 255, 254, 253 (8 keys each,
+    in that order) take 1020..1023 + 0..3, 1016..1019 + 4..7 and 1012..1015 +
+    8..11, so the head is [0, 12) and the split replays its wrapped entries
+    before the tail's, which then move past slot 1023; three more clusters
+    start in slots 1..30 ([16, 19), [24, 26), [28, 36): the `a0 <= 30` loop,
+    the last one reaching into word 1 with two entries of home line 8, whose
+    position 32 lies below U = 36: the unit places them, the sweep skips
+    them); the tail cluster starts at slot 980 with the trigger's full window
+    (T = 980),
+    so the wrap unit is 80 slots wide (< 128: the fast path).  Lines 100..104
+    add a cluster with a backlog for the sweep proper.  Every group alternates
+    its child bit key by key."""
+    img = []
+    for h, n in [(255, 8), (254, 8), (253, 8), (245, 32), (4, 3), (6, 2), (7, 6), (8, 2), (100, 12), (101, 4),
+                 (102, 4), (103, 4), (104, 4)]:
+        img += [(h, i & 1, 1) for i in range(n)]
+    return img
+
+
+def _wrap_drop_both_image():
+    """A fast-path wrap unit that drops entries of BOTH children (split_loss
+    drops from child 0 only).  Insert order and slots:
+      4 keys of line 255, child 1 -> 1020..1023;
+      28 keys of line 248, child 0 -> 992..1019 (its window is now full);
+      8 keys of line 250, child 0 -> wrap to 0..7;
+      20 keys of line 255, child 1 -> 8..27;  4 of line 0, child 1 -> 28..31;
+      4 each of lines 1..5, child 1 -> 32..35, 36..39, ..., 48..51.
+    The split replays the head [0, 52) first.  Child 0: line 250's 8 wrapped
+    entries take 1000..1007, so line 248's 28 entries find 24 free slots in
+    [992, 1024): 4 dropped.  Child 1: line 255's 20 head entries take
+    1020..1023 and 0..15 and line 0's, 1's and 2's take 16..27 -- line 255's
+    whole window -- so its 4 entries of the tail (parent 1020..1023) are
+    dropped.  Lines 3..5 land at 28..39, positions 60..71 of the unit's
+    128-bit map: line 4's window (map bits 48..79) is full below bit 64 and
+    continues above it, the one place where ext32 must join the map's two
+    words.  Lines 0..5 sit behind the wrapped entries in the head, so a sweep
+    that did not mask the positions below U = 52 would place them at their
+    home slots instead.  The unit is 84 slots wide."""
+    return [(255, 1, 4), (248, 0, 28), (250, 0, 8), (255, 1, 20)] + [(h, 1, 4) for h in range(6)]
+
+
+_WRAP_LINES = list(range(201, 256)) + list(range(0, 41))
+_WRAP_DROP_LINES = list(range(217, 256)) + list(range(0, 30))
+SPLIT_SHAPES = {
+    # a completely full parent: all_full -> the generic replay
+    "full_alt": dict(image=_per_line(range(256), lambda h: h & 1), trigger=(7, 1),
+                     occupied=1024, clusters=[(0, 1024)]),
+    "full_child0": dict(image=_per_line(range(256), 0), trigger=(7, 0), occupied=1024, clusters=[(0, 1024)]),
+    "full_shifted": dict(image=[(255, 1, 8)] + _per_line(range(254), 0), trigger=(100, 0),
+                         occupied=1024, clusters=[(0, 1024)]),
+    # one 628-slot cluster outside any wrap unit, a backlog of 28 over ~19 words of the sweep
+    "backlog_c0": dict(image=[(50, 0, 32)] + _per_line(range(51, 200), 0), trigger=(50, 0),
+                       occupied=628, clusters=[(200, 628)]),
+    "backlog_mixed": dict(image=[(50, 0, 32)] + _per_line(range(51, 200), lambda h: int(h % 3 == 0)),
+                          trigger=(50, 0), occupied=628, clusters=[(200, 628)]),
+    # a wrap unit wider than 128 slots: wide -> the generic replay
+    "wide_wrap": dict(image=[(200, 0, 32)] + _per_line(_WRAP_LINES, 0), trigger=(200, 1),
+                      occupied=416, clusters=[(800, 416)]),
+    "wide_wrap_mix": dict(image=[(200, 1, 32)] + _per_line(_WRAP_LINES, lambda h: h & 1), trigger=(200, 1),
+                          occupied=416, clusters=[(800, 416)]),
+    "wide_wrap_drop": dict(image=[(216, 0, 32)] + _per_line(_WRAP_DROP_LINES, 0), trigger=(216, 0),
+                           occupied=308, clusters=[(864, 308)]),
+    # the cluster path through a narrow wrap unit (see the image builders)
+    "cyclic_heads": dict(image=_cyclic_heads_image(), trigger=(245, 0), occupied=97,
+                         clusters=[(16, 3), (24, 2), (28, 8), (400, 28), (980, 56)]),
+    "wrap_drop_both": dict(image=_wrap_drop_both_image(), trigger=(248, 0), occupied=84, clusters=[(992, 84)]),
+}
+# name suffix -> (init_cap, hash prefix of the target segment, its local depth):
+# CCEH_hybrid(2)'s segment 0 (child bit = hash bit 62), and segment 0b1011 of
+# CCEH_hybrid(16) (child bit = hash bit 59; the split happens away from
+# segment 0 and doubles a depth-4 directory)
+SPLIT_SHAPE_TABLES = {"": (2, 0, 1), "_d4": (16, 0b1011, 4)}
+
+
+SPLIT_SHAPE_ABSENT = 120  # absent keys at a stream's end (every stream is > 256 ops from its first Get on)
+_SHAPE_POOLS = {}
+
+
+def split_shape_parts(name, hash64):
+    """Split shape `name` (a SPLIT_SHAPES name plus a SPLIT_SHAPE_TABLES
+    suffix) in parts: (init_cap, prefix, L, image keys in insert order,
+    trigger keys, absent keys)."""
+    base, suffix = (name[:-3], "_d4") if name.endswith("_d4") else (name, "")
+    init_cap, prefix, L = SPLIT_SHAPE_TABLES[suffix]
+    if suffix not in _SHAPE_POOLS:  # one pool per table, filtered once
+        _SHAPE_POOLS[suffix] = _key_cells(hash64, prefix, L)
+    take = _SHAPE_POOLS[suffix]()
+    sh = SPLIT_SHAPES[base]
+    image = np.concatenate([take(h, c, n) for h, c, n in sh["image"]])
+    trigger = take(*sh["trigger"])
+    absent = uniform_keys(901, 0, SPLIT_SHAPE_ABSENT)
+    return init_cap, prefix, L, image, trigger, absent
+
+
+def split_shapes(hash64):
+    """The crafted split images as streams, name -> (init_cap, convention, ops,
+    keys, values): the image inserts, Gets of every image key, the trigger
+    insert (its window is full: the segment splits), Gets of every image key
+    again and of SPLIT_SHAPE_ABSENT absent keys.  No split happens before the trigger.
+    SPLIT_SHAPES says what each image is and which branch of split_team
+    (bucket.hip) it pins; every shape comes for both SPLIT_SHAPE_TABLES."""
+    s = {}
+    for suffix in SPLIT_SHAPE_TABLES:
+        for base in SPLIT_SHAPES:
+            init_cap, _, _, image, trigger, absent = split_shape_parts(base + suffix, hash64)
+            keys = np.concatenate([image, image, trigger, image, absent])
+            ops = np.zeros(keys.size, np.uint8)
+            ops[:image.size] = OP_INSERT
+            ops[2 * image.size:2 * image.size + trigger.size] = OP_INSERT
+            vals = np.where(ops == OP_INSERT, _vals(keys, 0x5A17), np.uint64(0)).astype(np.uint64)
+            s[base + suffix] = (init_cap, "hybrid", ops, keys, vals)
+    return s
+
+
+def split_shape_image_size(keys):
+    """n of a split_shapes stream: n inserts, n Gets, the trigger, n Gets, the absent Gets."""
+    return (len(keys) - 1 - SPLIT_SHAPE_ABSENT) // 3
+
+
+def split_shape_get_values(g, ops, keys, vals):
+    """The reference's result of every Get of a split_shapes stream, in stream
+    order, from its fixture entry g: get_hits_hex has one bit per Get (a hit
+    returns the value the stream inserted with that key, no key is inserted
+    twice), and the rebuilt array must hash to the reference's
+    get_values_sha."""
+    gets = np.asarray(ops) == OP_GET
+    hit = np.unpackbits(np.frombuffer(bytes.fromhex(g["get_hits_hex"]), np.uint8))[:int(gets.sum())].astype(bool)
+    ins = ~gets
+    order = np.argsort(keys[ins], kind="stable")
+    ik, iv = keys[ins][order], vals[ins][order]
+    pos = np.minimum(np.searchsorted(ik, keys[gets]), ik.size - 1)
+    assert np.all(ik[pos][hit] == keys[gets][hit])
+    want = np.where(hit, iv[pos], np.uint64(0)).astype(np.uint64)
+    full = np.zeros(len(ops), np.uint64)
+    full[gets] = want
+    assert sha(full) == g["get_values_sha"] and int(hit.sum()) == g["get_hits"]
+    return want
+
+
+def occupancy_clusters(occ):
+    """Maximal runs of occupied slots of one segment (occ: 1024 booleans) as
+    sorted (first slot, length); the run through slot 1023 continues at 0."""
+    occ = np.asarray(occ, bool)
+    if occ.all():
+        return [(0, occ.size)]
+    starts = np.nonzero(occ & ~np.roll(occ, 1))[0]
+    out = []
+    for a in starts.tolist():
+        n = 0
+        while occ[(a + n) % occ.size]:
+            n += 1
+        out.append((a, n))
+    return out
+
+
 def split_loss(seed, hash64, mixed=False, n_fill=3000):
     """Insert4split's silent drop (CCEH_hybrid.cpp:18-28), through
-    the wrap unit.  CCEH_hybrid(2): segment 0 holds hash prefix 0; every key
+    the wrap unit (split_shapes below builds the other crafted split images).
+    CCEH_hybrid(2): segment 0 holds hash prefix 0; every key
     here has h >> 62 == 0 (segment 0, and child 0 of its first split).
       A: 32 keys of home line 248 fill the window [992, 1024);
       B: 28 keys of home line 255 (window [1020, 1052) mod 1024) find

@@ -90,6 +90,95 @@ def test_oracle_matches_reference(name, cceh_golden):
 
 
 @pytest.fixture(scope="module")
+def split_shapes_golden(golden_dir):
+    with open(os.path.join(golden_dir, "split_shapes.json")) as f:
+        return json.load(f)
+
+
+SHAPES = None
+SHAPE_NAMES = [b + s for s in S.SPLIT_SHAPE_TABLES for b in S.SPLIT_SHAPES]
+
+
+def _shapes():
+    global SHAPES
+    if SHAPES is None:
+        SHAPES = S.split_shapes(O.hash64)
+    return SHAPES
+
+
+@pytest.mark.parametrize("name", SHAPE_NAMES)
+def test_oracle_split_shapes_match_reference(name, split_shapes_golden):
+    """The crafted split images (scenarios.split_shapes) through the oracle
+    equal the reference's own run (tests/golden/split_shapes.json): depth,
+    segment images, dropped entries and the result of every single Get."""
+    g = split_shapes_golden[name]
+    init_cap, conv, ops, keys, vals = _shapes()[name]
+    assert keys.size == g["n_ops"]
+    t = O.OracleCCEH(O.OracleCCEH.depth_for_hybrid(init_cap))
+    out, st = t.mixed(ops, keys, vals)
+    d = t.dump()
+    rec = S.summarize(d["depth"], d["local_depth"], d["prefix"], d["keys"], d["values"], out, ops)
+    for k, v in rec.items():
+        assert v == g[k], (name, k)
+    gets = ops == S.OP_GET
+    want = S.split_shape_get_values(g, ops, keys, vals)
+    assert want.size == g["n_gets"] == int(gets.sum())
+    assert np.array_equal(out[gets], want)
+    assert np.all(st[~gets] == O.ST_INSERTED)
+    assert np.array_equal(st[gets] == O.ST_HIT, want != 0)
+    stats = t.stats()
+    assert stats["split_loss"] == g["split_loss"] == int((~gets).sum()) - g["occupied"]
+    assert stats["early_exit_mismatch"] == 0
+    assert abs(t.utilization() - g["utilization"]) < 1e-9 and t.capacity() == g["capacity"]
+    # a dropped key misses afterwards, and nothing else of the image does
+    n_img = S.split_shape_image_size(keys)
+    assert int((out[2 * n_img + 1: 3 * n_img + 1] == 0).sum()) == g["split_loss"]
+    assert np.all(out[n_img:2 * n_img] == vals[:n_img]) and np.all(out[3 * n_img + 1:] == 0)
+
+
+@pytest.mark.parametrize("name", SHAPE_NAMES)
+def test_split_shapes_are_what_they_claim(name):
+    """Each builder really makes its shape (a change of uniform_keys or hash64
+    would otherwise turn these back into ordinary streams): after the image
+    inserts and the first Gets nothing has split, every image key sits in the
+    target segment, whose occupancy and clusters are the designed ones, every
+    key is on its line and child bit, the trigger's window is full -- and the
+    trigger then splits exactly that segment."""
+    base = name[:-3] if name.endswith("_d4") else name
+    sh = S.SPLIT_SHAPES[base]
+    init_cap, prefix, L, image, trigger, absent = S.split_shape_parts(name, O.hash64)
+    _, _, ops, keys, vals = _shapes()[name]
+    n = image.size
+    assert np.array_equal(keys[:n], image) and np.all(ops[:n] == S.OP_INSERT) and np.all(ops[n:2 * n] == S.OP_GET)
+    assert ops[2 * n] == S.OP_INSERT and keys[2 * n] == trigger[0] and np.all(ops[2 * n + 1:] == S.OP_GET)
+    assert np.unique(np.concatenate([image, trigger, absent])).size == n + 1 + absent.size
+    h = O.hash64(np.concatenate([image, trigger]))
+    assert np.all(h >> np.uint64(64 - L) == np.uint64(prefix))
+    lines = [ln for ln, _, c in sh["image"] for _ in range(c)] + [sh["trigger"][0]]
+    child = [ch for _, ch, c in sh["image"] for _ in range(c)] + [sh["trigger"][1]]
+    assert (h & np.uint64(0xFF)).tolist() == lines
+    assert ((h >> np.uint64(63 - L)) & np.uint64(1)).tolist() == child
+    t = O.OracleCCEH(O.OracleCCEH.depth_for_hybrid(init_cap))
+    assert t.depth == L  # the target segment is one of the initial ones
+    out, _ = t.mixed(ops[:2 * n], keys[:2 * n], vals[:2 * n])
+    assert t.stats()["splits"] == 0 and np.array_equal(out[n:], vals[:n])
+    d = t.dump()
+    seg = int(np.nonzero(d["prefix"] == prefix)[0][0])
+    assert d["local_depth"][seg] == L
+    sk = d["keys"].reshape(-1, 1024)
+    occ = sk[seg] != np.uint64(2**64 - 1)
+    assert int(occ.sum()) == sh["occupied"] == n == int((sk != np.uint64(2**64 - 1)).sum())
+    assert S.occupancy_clusters(occ) == sh["clusters"]
+    w = (4 * sh["trigger"][0] + np.arange(32)) % 1024
+    assert occ[w].all()  # the trigger's window is full
+    t.insert(trigger, trigger)
+    d2 = t.dump()
+    assert t.stats()["splits"] >= 1 and d2["local_depth"].size > d["local_depth"].size
+    grown = d2["prefix"][d2["local_depth"] > L] >> (d2["local_depth"][d2["local_depth"] > L] - L).astype(np.uint64)
+    assert np.all(grown == prefix)  # only the target segment split
+
+
+@pytest.fixture(scope="module")
 def findany_golden(golden_dir):
     with open(os.path.join(golden_dir, "findany.json")) as f:
         return json.load(f)
