@@ -5,16 +5,17 @@ CSRC := pmdfc_amd/csrc
 LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/cceh_engine.hip
-HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h include/pmdfc_cceh.h
+SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/cceh_engine.hip
+HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h include/pmdfc_cceh.h
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
 HOSTLIB := $(LIBDIR)/libpmdfc_gpucceh.so
 HOSTHDRS := pmdfc_amd/host/batch_core.h pmdfc_amd/host/gpu_cceh.h pmdfc_amd/host/gpu_cceh_hybrid.h pmdfc_amd/host/iface_compat.h include/pmdfc_cceh.h
 KVTEST := $(LIBDIR)/test_gpu_kv
 FRONTBENCH := $(LIBDIR)/bench_frontend
+IMGKVTEST := $(LIBDIR)/test_gpu_image_kv
 
-all: $(LIB) $(HOSTLIB) $(KVTEST) $(FRONTBENCH) oracle
+all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(FRONTBENCH) oracle
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -28,6 +29,9 @@ $(HOSTLIB): pmdfc_amd/host/batch_core.cpp pmdfc_amd/host/kv_capi.cpp include/pmd
 
 $(KVTEST): tests/cpp/test_gpu_kv.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
+
+$(IMGKVTEST): tests/cpp/test_gpu_image_kv.cpp $(HOSTLIB)
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_image_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(FRONTBENCH): tools/bench_frontend.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tools/bench_frontend.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'

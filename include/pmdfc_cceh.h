@@ -268,6 +268,40 @@ int pmdfc_cceh_utilization(pmdfc_cceh_t* t, double* out);
 int pmdfc_cceh_dump(pmdfc_cceh_t* t, uint32_t* dir_canon, uint32_t* local_depth,
                     uint64_t* prefix, uint64_t* keys, uint64_t* values, uint64_t* nseg_out);
 
+/* ---- table image: snapshot and restore (synchronous) ------------------
+ * The image is one contiguous buffer (pmdfc_amd/csrc/image.h):
+ * a 4,096-byte little-endian header (magic "PMDFCIMG", version 1,
+ * initial_depth, shard_bits, shard_id, global depth, min and max local depth,
+ * segment count, live entries, total bytes; unused bytes zero), the local
+ * depths in canonical order padded to a multiple of 4,096 bytes, then the
+ * segment images in canonical order (values of empty slots 0) -- the canonical
+ * dump of pmdfc_cceh_dump and nothing else: no segment ids, pool offsets,
+ * directory entries or occupancy words.  Two engines holding the same table
+ * give the same bytes, however they were batched.
+ * buf: 16-byte aligned device memory, or pinned host memory mapped into the
+ * device.  Both calls synchronise the device first, like stats and dump. */
+/* Writes the image of t to buf and its size to *bytes_out; t is unchanged.
+ * buf == NULL or cap_bytes too small: PMDFC_ERR_SIZE with *bytes_out set to
+ * the size needed, nothing written. */
+int pmdfc_cceh_snapshot(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t* bytes_out, void* stream);
+/* Replaces the whole table of t with the image.  t must have the image's
+ * initial_depth, shard_bits and shard_id (else PMDFC_ERR_ARG); max_batch,
+ * max_segments and PMDFC_CFG_UPSERT may differ from the engine that wrote it.
+ * PMDFC_ERR_ARG: an image the validation refuses (magic, version, byte counts,
+ * a local depth outside [initial_depth, 30], local depths that do not tile
+ * the shard's hash space exactly, a header that disagrees with them);
+ * PMDFC_ERR_SIZE: more segments than max_segments, or the rebuilt
+ * sub-directories do not fit the pool.  All of these are decided on the host
+ * from the header and the local depths and leave the table exactly as it was.
+ * The device pass then hashes every live key: if any lies outside its
+ * segment's hash prefix (or is a reserved key) the call returns PMDFC_ERR_ARG
+ * and leaves the table in the freshly reset state (pmdfc_cceh_reset).
+ * After PMDFC_OK depth, segments, capacity, Utilization, dump, Get, FindAnyway
+ * and every later Insert / mixed batch are those of the source table; the
+ * history counters of pmdfc_cceh_stats (splits, doublings, split_loss, passes,
+ * runs, batches, error_flags, ...) start from zero, as after a reset. */
+int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* stream);
+
 /* ---- kernel timing (HIP events on the launching stream) -------------- */
 /* kernel classes */
 #define PMDFC_K_GET 0

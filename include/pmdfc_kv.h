@@ -93,6 +93,13 @@ int pmdfc_kv_find_anyway(pmdfc_kv_t* kv, uint64_t key, uint64_t* value, uint8_t*
 int pmdfc_kv_stats(pmdfc_kv_t* kv, pmdfc_cceh_stats_t* out);
 int pmdfc_kv_dump(pmdfc_kv_t* kv, uint64_t dir_cap, uint64_t seg_cap, uint32_t* dir_canon, uint32_t* local_depth,
                   uint64_t* prefix, uint64_t* keys, uint64_t* values, uint64_t* nseg_out, uint64_t* ndir_out);
+/* The table image (pmdfc_cceh.h, snapshot and restore) as a file of its raw
+ * bytes, after every queued op, the serving waves stopped meanwhile.  load
+ * replaces the whole table with the file's; the refusals are those of the
+ * restore call, plus PMDFC_ERR_ARG for a file that cannot be read or written.  An
+ * attached counting BF is neither saved nor rebuilt. */
+int pmdfc_kv_save(pmdfc_kv_t* kv, const char* path);
+int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path);
 /* counters: [0] serving-wave launches, [1] device chunks (wave chunks +
  * flood batches), [2] flood batches, [3] ops in flood batches, [4] failed
  * ops, [5] ops completed, [6] serving waves per launch, [7] header reloads

@@ -6,3 +6,4 @@ from .engine import (CCEH, Comm, BloomFilter, CountingBloomFilter, TraceReader, 
                      ST_INSERTED, ST_RESERVED_KEY, ST_UNSPLITTABLE, ST_DEPTH_LIMIT, ST_CAPACITY,
                      ST_FILTERED, ST_WRONG_SHARD, ST_ROUTE_OVERFLOW, ST_SPLIT_LOST, ST_UPDATED, CFG_UPSERT)
 from .kv import KV  # noqa: F401,E402
+from . import image  # noqa: F401,E402

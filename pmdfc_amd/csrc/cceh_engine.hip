@@ -14,6 +14,7 @@
 //   <= 64 ops : k_mixed_tiny; <= 256: k_mixed_small (1 launch)
 //   <= 8192   : k_part (one block) -> k_medium (2 launches)
 //   Get    : k_get_u (1 launch; k_flatten first after inserts)
+//   snapshot / restore (synchronous): image.hip
 // Splits and directory growth are decided and done on the device (per-bucket
 // sub-directories), so a batch never needs a host decision; only a table
 // still coarser than its bucket resolution syncs once per sub-batch.
@@ -32,6 +33,7 @@
 #include "../../include/pmdfc_cceh.h"
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "image.h"
 #include "knobs.h"
 
 using namespace pmdfc;
@@ -494,13 +496,15 @@ static int clear_key_set(pmdfc_cceh* t, hipStream_t s) {
   return PMDFC_OK;
 }
 
-static int init_state(pmdfc_cceh* t, hipStream_t s) {
-  const uint32_t n0 = 1u << (t->D0 - t->sbits);
+// The host side of a table that starts over (a reset, or a restore of an
+// image): p1 directory bucket bits, every segment at least min_ld deep, no
+// batch run yet.
+static int start_host_state(pmdfc_cceh* t, hipStream_t s, uint32_t p1, uint32_t min_ld) {
   // (no earlier rebucket_now copy may land after the seed below: the event
   // is recorded right after that copy -- a device-wide sync would also wait
   // for every other stream, a serving wave included)
   if (t->minld_pending) HIPCHK(hipEventSynchronize(t->ev_minld));
-  __atomic_store_n(&t->h_depth[1], t->D0, __ATOMIC_RELEASE);
+  __atomic_store_n(&t->h_depth[1], min_ld, __ATOMIC_RELEASE);
   t->minld_pending = false;
   // the mixed batches' key set is empty between batches (each batch's verify
   // pass empties the slots it used), so a reset leaves it alone -- unless it
@@ -511,13 +515,19 @@ static int init_state(pmdfc_cceh* t, hipStream_t s) {
     if (int rc = clear_key_set(t, s)) return rc;
     t->iset_dirty = false;
   }
-  t->p1 = t->p1_init;
-  const uint32_t region = kFixedSlot << t->p1max;  // the fixed slots come first in the pool
-  const uint32_t db0 = t->D0 - t->sbits - t->p1;
-  const uint32_t fixed = (t->p1 == t->p1max && db0 <= kFixedBits) ? 1u : 0u;
-  // the segments, the passes' per-bucket words and the control block with
-  // the hint, in ONE kernel on s: a reset queues behind the work before it
-  // without a host sync (the bench resets the table at every step)
+  t->p1 = p1;
+  t->clean_sbb = ~0u;
+  t->batches = 0;
+  t->parity = 0;
+  t->rb = 0;
+  t->flat_valid = false;
+  return PMDFC_OK;
+}
+
+// the per-batch words a starting table needs zero (the kernel that starts its
+// control block zeroes them in the same launch): the record cursors, the stat
+// slots, the worklist counts, the decline flags, the grants, the grant shards
+static InitZero batch_words(const pmdfc_cceh* t) {
   InitZero z{};
   z.p[0] = t->cursor;
   z.n[0] = (uint64_t)kRecBufs * t->cblk;
@@ -531,13 +541,20 @@ static int init_state(pmdfc_cceh* t, hipStream_t s) {
   z.n[4] = 1ULL << t->p1max;
   z.p[5] = reinterpret_cast<uint32_t*>(t->gsh);
   z.n[5] = 2ULL * 2 * kGShards * kGStride;
-  launch_init_segments(t->pairs, t->occ, t->ldep, t->pool, t->hdr, n0, t->D0, t->p1, fixed, region, z, t->ctl,
-                       region + (fixed ? 0u : n0), t->d_hint, s);
-  t->clean_sbb = ~0u;
-  t->batches = 0;
-  t->parity = 0;
-  t->rb = 0;
-  t->flat_valid = false;
+  return z;
+}
+
+static int init_state(pmdfc_cceh* t, hipStream_t s) {
+  const uint32_t n0 = 1u << (t->D0 - t->sbits);
+  if (int rc = start_host_state(t, s, t->p1_init, t->D0)) return rc;
+  const uint32_t region = kFixedSlot << t->p1max;  // the fixed slots come first in the pool
+  const uint32_t db0 = t->D0 - t->sbits - t->p1;
+  const uint32_t fixed = (t->p1 == t->p1max && db0 <= kFixedBits) ? 1u : 0u;
+  // the segments, the passes' per-bucket words and the control block with
+  // the hint, in ONE kernel on s: a reset queues behind the work before it
+  // without a host sync (the bench resets the table at every step)
+  launch_init_segments(t->pairs, t->occ, t->ldep, t->pool, t->hdr, n0, t->D0, t->p1, fixed, region, batch_words(t),
+                       t->ctl, region + (fixed ? 0u : n0), t->d_hint, s);
   return PMDFC_OK;
 }
 
@@ -1549,6 +1566,170 @@ int pmdfc_cceh_dump(pmdfc_cceh_t* t, uint32_t* dir_canon, uint32_t* local_depth,
         if (values) values[i * kSlots + j] = buf[j].x == kInvalid ? 0 : buf[j].y;
       }
     }
+  }
+  return PMDFC_OK;
+}
+
+// ---- table image (image.h, image.hip)
+
+namespace {
+struct DevTmp {  // a device allocation that lives for one synchronous call
+  void* p = nullptr;
+  ~DevTmp() {
+    if (p) (void)hipFree(p);
+  }
+};
+}  // namespace
+
+int pmdfc_cceh_snapshot(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t* bytes_out, void* stream) {
+  if (!t || !bytes_out) return fail(PMDFC_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipDeviceSynchronize());
+  // canonical order: the segments of each bucket counted, the counts scanned
+  const uint32_t nb = 1u << t->p1;
+  DevTmp wk;
+  HIPCHK(hipMalloc(&wk.p, (2ull * nb + 1) * sizeof(uint32_t)));
+  uint32_t* cnt = static_cast<uint32_t*>(wk.p);
+  uint32_t *base = cnt + nb, *total = base + nb;
+  launch_image_count(t->hdr, t->pool, (uint32_t)t->pool_cap, t->p1, t->sbits, cnt, base, total, s);
+  HIPCHK(hipGetLastError());
+  uint32_t nseg = 0;
+  HIPCHK(hipMemcpyAsync(&nseg, total, sizeof nseg, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (nseg == 0 || nseg > t->max_segs) return fail(PMDFC_ERR_STATE, "snapshot: the directory walk found no sound table");
+  const uint64_t need = image::total_bytes(nseg);
+  *bytes_out = need;
+  if (!buf || cap_bytes < need) return fail(PMDFC_ERR_SIZE, "snapshot: the buffer is smaller than the image");
+  if ((uintptr_t)buf & 15u) return fail(PMDFC_ERR_ARG, "snapshot: the buffer must be 16-byte aligned");
+  uint8_t* out = static_cast<uint8_t*>(buf);
+  DevTmp ord;
+  HIPCHK(hipMalloc(&ord.p, (uint64_t)nseg * sizeof(uint32_t)));
+  uint32_t* order = static_cast<uint32_t*>(ord.p);
+  const uint64_t dbytes = image::depth_bytes(nseg);
+  HIPCHK(hipMemsetAsync(out + image::kHeaderBytes, 0, dbytes, s));
+  launch_image_emit(t->hdr, t->pool, (uint32_t)t->pool_cap, t->p1, t->sbits, base, nseg, order,
+                    out + image::kHeaderBytes, s);
+  launch_image_gather(t->pairs, order, nseg, (uint32_t)t->max_segs,
+                      reinterpret_cast<ulonglong2*>(out + image::pairs_offset(nseg)), s);
+  HIPCHK(hipGetLastError());
+  // the live entries from the occupancy words, as Utilization counts them
+  if (int rc = read_ctl(t, s)) return rc;
+  const uint64_t nsegs = std::min<uint64_t>(t->hctl->nsegs, t->max_segs);
+  HIPCHK(hipMemsetAsync(t->popc, 0, sizeof(unsigned long long), s));
+  launch_popcount(t->occ, nsegs * 32, t->popc, s);
+  unsigned long long live = 0;
+  std::vector<uint8_t> ld(dbytes);
+  HIPCHK(hipMemcpyAsync(&live, t->popc, sizeof live, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ld.data(), out + image::kHeaderBytes, dbytes, hipMemcpyDefault, s));
+  HIPCHK(hipStreamSynchronize(s));
+  image::Header h;
+  h.initial_depth = t->D0;
+  h.shard_bits = t->sbits;
+  h.shard_id = t->shard;
+  h.nseg = nseg;
+  h.live = live;
+  h.total_bytes = need;
+  h.min_ld = *std::min_element(ld.begin(), ld.begin() + nseg);
+  h.max_ld = *std::max_element(ld.begin(), ld.begin() + nseg);
+  h.depth = std::max(t->D0, h.max_ld);
+  // (what this call wrote must be what pmdfc_cceh_restore accepts)
+  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_STATE, image::error_string(e));
+  std::vector<uint8_t> hb(image::kHeaderBytes);
+  image::encode_header(h, hb.data());
+  HIPCHK(hipMemcpy(out, hb.data(), hb.size(), hipMemcpyDefault));
+  return PMDFC_OK;
+}
+
+int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* stream) {
+  if (!t || !buf) return fail(PMDFC_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipDeviceSynchronize());
+  if ((uintptr_t)buf & 15u) return fail(PMDFC_ERR_ARG, "restore: the image must be 16-byte aligned");
+  if (bytes < image::kHeaderBytes) return fail(PMDFC_ERR_ARG, image::error_string(image::kShort));
+  const uint8_t* in = static_cast<const uint8_t*>(buf);
+  // ---- decided on the host, the table untouched: header, local depths, fit
+  std::vector<uint8_t> hb(image::kHeaderBytes);
+  HIPCHK(hipMemcpy(hb.data(), in, hb.size(), hipMemcpyDefault));
+  image::Header h;
+  if (int e = image::parse_header(hb.data(), bytes, &h)) return fail(PMDFC_ERR_ARG, image::error_string(e));
+  if (h.initial_depth != t->D0 || h.shard_bits != t->sbits || h.shard_id != t->shard)
+    return fail(PMDFC_ERR_ARG, "restore: the image's initial_depth / shard_bits / shard_id are not this engine's");
+  std::vector<uint8_t> ld(image::depth_bytes(h.nseg));
+  HIPCHK(hipMemcpy(ld.data(), in + image::kHeaderBytes, ld.size(), hipMemcpyDefault));
+  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_ARG, image::error_string(e));
+  if (h.nseg > t->max_segs) return fail(PMDFC_ERR_SIZE, "restore: the image has more segments than max_segments");
+  const uint32_t nseg = (uint32_t)h.nseg;
+  // the directory: the bucket bits rebucket_now would have reached, each
+  // bucket's sub-directory as deep as its deepest segment, in its fixed slot
+  // or past the reserved region (the rule of k_init_segments and the growth paths)
+  const uint32_t p1 = std::min<uint32_t>(t->p1max, h.min_ld - t->sbits);
+  const uint32_t top = kMaxDepth - t->sbits;
+  std::vector<uint2> desc(nseg);
+  std::vector<uint8_t> maxl(1u << p1, 0);
+  ImageCtl c{};
+  {
+    uint32_t pos = 0;  // in units of 2^-30 of the whole hash space
+    for (uint32_t i = 0; i < nseg; ++i) {
+      const uint32_t L = ld[i];
+      const uint32_t w = p1 ? pos >> (top - p1) : 0u;
+      maxl[w] = std::max<uint8_t>(maxl[w], (uint8_t)L);
+      desc[i] = make_uint2(pos, L);
+      c.depth_count[L] += 1;
+      pos += 1u << (kMaxDepth - L);
+    }
+  }
+  std::vector<uint64_t> hd(1u << p1);
+  const uint64_t region = (uint64_t)kFixedSlot << t->p1max;
+  uint64_t cur = region;
+  for (uint32_t w = 0; w < hd.size(); ++w) {
+    const uint32_t db = maxl[w] - t->sbits - p1;
+    if (p1 == t->p1max && db <= kFixedBits) {
+      hd[w] = hdr_make(w * kFixedSlot, db);
+    } else {
+      if (cur + (1ULL << db) > t->pool_cap) return fail(PMDFC_ERR_SIZE, "restore: the sub-directories do not fit the pool");
+      hd[w] = hdr_make((uint32_t)cur, db);
+      cur += 1ULL << db;
+    }
+  }
+  c.nsegs = nseg;
+  c.pool_cur = (uint32_t)cur;
+  c.max_ld = h.max_ld;
+  DevTmp dv;  // the descriptors, then the prefix check's count
+  HIPCHK(hipMalloc(&dv.p, (uint64_t)nseg * sizeof(uint2) + sizeof(uint32_t)));
+  uint2* d_desc = static_cast<uint2*>(dv.p);
+  uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_desc + nseg);
+  // ---- from here the table is the image's
+  HIPCHK(hipMemcpy(d_desc, desc.data(), (uint64_t)nseg * sizeof(uint2), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(d_bad, 0, sizeof(uint32_t)));
+  HIPCHK(hipMemcpy(t->hdr, hd.data(), hd.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if (int rc = start_host_state(t, s, p1, h.min_ld)) return rc;
+  launch_image_ctl(batch_words(t), t->ctl, c, t->d_hint, s);
+  ScatterArgs a{};
+  a.img = reinterpret_cast<const ulonglong2*>(in + image::pairs_offset(nseg));
+  a.desc = d_desc;
+  a.hdr = t->hdr;
+  a.nseg = nseg;
+  a.p1 = p1;
+  a.sbits = t->sbits;
+  a.shard = t->shard;
+  a.pairs = t->pairs;
+  a.occ = t->occ;
+  a.ldep = t->ldep;
+  a.pool = t->pool;
+  a.bad = d_bad;
+  launch_image_scatter(a, s);
+  HIPCHK(hipGetLastError());
+  uint32_t bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad) {
+    if (int rc = init_state(t, s)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return fail(PMDFC_ERR_ARG, "restore: live keys outside their segment's hash prefix (the table was reset)");
   }
   return PMDFC_OK;
 }

@@ -78,6 +78,70 @@ void launch_init_segments(ulonglong2* pairs, uint32_t* occ, uint8_t* ldep, uint3
                           uint64_t* hdr, uint32_t nseg, uint32_t depth, uint32_t p1, uint32_t fixed,
                           uint32_t region, const InitZero& z, DevCtl* ctl, uint32_t pool_cur, uint32_t* hint,
                           hipStream_t s);
+#ifdef __HIPCC__
+// What a fresh table (k_init_segments) and a restored one (k_image_ctl) share.
+// Thread i of the grid zeroes word i of each array of z.
+__device__ __forceinline__ void zero_batch_words(const InitZero& z, uint64_t i) {
+#pragma unroll
+  for (int k = 0; k < kInitZero; ++k)
+    if (i < z.n[k]) z.p[k][i] = 0;
+}
+// One whole block of 256 threads: the control block of a table of nsegs
+// segments with every counter zero, and the host-mapped segment-count hint.
+// True on the one thread that then fills in depth_count[].
+__device__ __forceinline__ bool start_ctl(DevCtl* ctl, uint32_t nsegs, uint32_t max_ld, uint32_t pool_cur,
+                                          uint32_t* hint) {
+  uint32_t* w = reinterpret_cast<uint32_t*>(ctl);
+  for (uint32_t j = threadIdx.x; j < sizeof(DevCtl) / 4; j += 256) w[j] = 0;
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  ctl->nsegs = nsegs;
+  ctl->max_ld = max_ld;
+  ctl->pool_cur = pool_cur;
+  if (hint) __hip_atomic_store(hint, nsegs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return true;
+}
+#endif
+
+// image.hip (pmdfc_cceh_snapshot / pmdfc_cceh_restore, image.h)
+// Canonical order on the device, the walk of pmdfc_cceh_dump: cnt[w] = the
+// distinct segments of bucket w (an entry is a segment's first when its index
+// in the sub-directory is a multiple of the segment's stride); base[] = their
+// exclusive scan over the 2^p1 buckets, *total the segment count; then
+// order[i] = the directory entry {arena id, local depth} of canonical segment
+// i and ld_out[i] its local depth (i < nseg).
+void launch_image_count(const uint64_t* hdr, const uint32_t* pool, uint32_t pool_cap, uint32_t p1, uint32_t sbits,
+                        uint32_t* cnt, uint32_t* base, uint32_t* total, hipStream_t s);
+void launch_image_emit(const uint64_t* hdr, const uint32_t* pool, uint32_t pool_cap, uint32_t p1, uint32_t sbits,
+                       const uint32_t* base, uint32_t nseg, uint32_t* order, uint8_t* ld_out, hipStream_t s);
+// the 16 KiB of arena segment de_seg(order[i]) -> out + i * 1024, the values
+// of empty slots zeroed
+void launch_image_gather(const ulonglong2* pairs, const uint32_t* order, uint32_t nseg, uint32_t max_segs,
+                         ulonglong2* out, hipStream_t s);
+// Restore.  Everything the kernels index with comes from the host, which
+// derived it from validated local depths: desc[i] = {segment i's start in the
+// shard's hash space in units of 2^-30 of the whole space, local depth}, hdr
+// the rebuilt bucket headers (already on the device).
+struct ImageCtl {
+  uint32_t nsegs, pool_cur, max_ld;
+  uint32_t depth_count[32];
+};
+// the per-batch words zeroed and the control block set, as k_init_segments does
+void launch_image_ctl(const InitZero& z, DevCtl* ctl, const ImageCtl& c, uint32_t* hint, hipStream_t s);
+struct ScatterArgs {
+  const ulonglong2* img;  // nseg x 1024 pairs in canonical order
+  const uint2* desc;
+  const uint64_t* hdr;
+  uint32_t nseg, p1, sbits, shard;
+  ulonglong2* pairs;
+  uint32_t* occ;
+  uint8_t* ldep;
+  uint32_t* pool;
+  uint32_t* bad;  // += live keys whose hash prefix is not their segment's, and reserved keys
+};
+// segment i of the image -> arena id i: pairs, occupancy words, local depth,
+// its directory entries; the live keys are hashed against the segment's prefix
+void launch_image_scatter(const ScatterArgs& a, hipStream_t s);
 // flatten the bucketed directory for pure-Get batches: *bits = p1 + max db
 // (the physical depth), flat[x] = the sub-directory entry of index x
 void launch_flatten(const uint64_t* hdr, const uint32_t* pool, uint32_t p1, uint32_t* flat,

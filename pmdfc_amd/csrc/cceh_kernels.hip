@@ -955,21 +955,8 @@ __global__ __launch_bounds__(256) void k_init_segments(ulonglong2* __restrict__ 
   }
   const uint32_t nb = 1u << p1;
   if (i < nb) hdr[i] = hdr_make(fixed ? (uint32_t)i * kFixedSlot : region + ((uint32_t)i << db0), db0);
-#pragma unroll
-  for (int k = 0; k < kInitZero; ++k)
-    if (i < z.n[k]) z.p[k][i] = 0;
-  if (blockIdx.x == 0) {
-    uint32_t* w = reinterpret_cast<uint32_t*>(ctl);
-    for (uint32_t j = threadIdx.x; j < sizeof(DevCtl) / 4; j += 256) w[j] = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      ctl->nsegs = nseg;
-      ctl->max_ld = depth;
-      ctl->pool_cur = pool_cur;
-      ctl->depth_count[depth] = nseg;
-      if (hint) __hip_atomic_store(hint, nseg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  zero_batch_words(z, i);
+  if (blockIdx.x == 0 && start_ctl(ctl, nseg, depth, pool_cur, hint)) ctl->depth_count[depth] = nseg;
 }
 
 // Finer directory buckets (p1 -> p1n bits) once every segment's local depth

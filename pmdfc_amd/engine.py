@@ -85,6 +85,7 @@ EXPORTS = [
     "pmdfc_cceh_serve_start", "pmdfc_cceh_serve_start_n", "pmdfc_cceh_serve_waves_max", "pmdfc_comm_id", "pmdfc_comm_create", "pmdfc_comm_create_host", "pmdfc_comm_destroy",
     "pmdfc_route_batches",
     "pmdfc_route_mixed_batches",
+    "pmdfc_cceh_snapshot", "pmdfc_cceh_restore",
 ]
 
 
@@ -177,6 +178,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_comm_destroy": (i32, [P]),
         "pmdfc_route_batches": (i32, [P, P, P, u32, P, P, P, u64, u32, P, P, P]),
         "pmdfc_route_mixed_batches": (i32, [P, P, P, P, P, P, P, u64, P, P, P]),
+        "pmdfc_cceh_snapshot": (i32, [P, P, u64, C.POINTER(u64), P]),
+        "pmdfc_cceh_restore": (i32, [P, P, u64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -469,7 +472,8 @@ class CCEH:
 
     def Recovery(self) -> bool:
         """CCEH::Recovery (CCEH_hybrid.cpp:391-410) repairs directory entries of
-        a crashed PMEM image; the device index is volatile, nothing to repair."""
+        a crashed PMEM image; the device index is volatile, nothing to repair
+        (a table survives a restart through save() / load())."""
         return False
 
     def Utilization(self) -> float:
@@ -506,6 +510,59 @@ class CCEH:
                                  keys.ctypes.data, vals.ctypes.data, C.byref(n)), "dump")
         return {"depth": d, "dir_canon": dir_canon, "local_depth": ld, "prefix": prefix,
                 "keys": keys, "values": vals}
+
+    # ---- table image (include/pmdfc_cceh.h; the format: pmdfc_amd/image.py)
+    def snapshot(self) -> torch.Tensor:
+        """The table's image as a uint8 tensor on the engine's device.  The
+        table is unchanged.  Two tables with the same canonical dump give the
+        same bytes."""
+        L = load_library()
+        n = C.c_uint64()
+        rc = L.pmdfc_cceh_snapshot(self._h, None, 0, C.byref(n), self._d.stream())
+        if rc != PMDFC_ERR_SIZE:  # (the sizing call's only good answer)
+            msg = L.pmdfc_last_error()
+            raise PmdfcError(f"snapshot sizing failed ({rc}): {msg.decode() if msg else ''}")
+        buf = torch.empty(n.value, dtype=torch.uint8, device=self._d.device)
+        _check(L.pmdfc_cceh_snapshot(self._h, buf.data_ptr(), buf.numel(), C.byref(n), self._d.stream()), "snapshot")
+        return buf[: n.value]
+
+    def restore(self, image):
+        """Replace the whole table with an image (a uint8 tensor, a numpy
+        array or bytes): one from snapshot(), a file of save(), or
+        pmdfc_amd.image.image_from_dump.  The engine must have the image's
+        initial depth, shard_bits and shard_id; max_batch, max_segments and
+        upsert may differ.  Raises PmdfcError for an image the engine refuses
+        (the table is then unchanged, or freshly reset if a key lay outside
+        its segment's hash prefix).  The history counters of stats() restart
+        from zero, as after reset()."""
+        if isinstance(image, torch.Tensor):
+            buf = image.to(self._d.device, torch.uint8).contiguous().reshape(-1)
+        else:
+            if isinstance(image, (bytes, bytearray, memoryview)):
+                image = np.frombuffer(image, dtype=np.uint8)
+            a = np.ascontiguousarray(image).view(np.uint8).reshape(-1)
+            buf = torch.from_numpy(a.copy() if not a.flags.writeable else a).to(self._d.device)
+        _check(load_library().pmdfc_cceh_restore(self._h, buf.data_ptr(), buf.numel(), self._d.stream()), "restore")
+
+    def save(self, path) -> int:
+        """snapshot() to a file of the raw image bytes, through a pinned host
+        buffer.  Returns the byte count."""
+        img = self.snapshot()
+        host = torch.empty(img.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(img)
+        with open(path, "wb") as f:
+            f.write(memoryview(host.numpy()))
+        return host.numel()
+
+    def load(self, path):
+        """restore() from a file written by save() (or by KV.save)."""
+        size = os.path.getsize(path)
+        host = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+        with open(path, "rb") as f:
+            got = f.readinto(memoryview(host.numpy()))
+        if got != size:
+            raise PmdfcError(f"{path}: short read")
+        self.restore(host.to(self._d.device))
 
     def timing(self, events: bool = True, count_lines: bool = False):
         flags = (1 if events else 0) | (2 if count_lines else 0)

@@ -999,6 +999,80 @@ int BatchCore::Dump(uint64_t dir_cap, uint64_t seg_cap, uint32_t* dir_canon, uin
   return rc;
 }
 
+// ---------------------------------------------------------------- table image
+
+namespace {
+// pinned host memory mapped into the device: the engine writes / reads the
+// image in place (pmdfc_cceh_snapshot / pmdfc_cceh_restore)
+struct MappedBuf {
+  void *host = nullptr, *dev = nullptr;
+  bool alloc(uint64_t bytes) {
+    if (hipHostMalloc(&host, bytes, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) {
+      host = nullptr;
+      return false;
+    }
+    return hipHostGetDevicePointer(&dev, host, 0) == hipSuccess;
+  }
+  ~MappedBuf() {
+    if (host) (void)hipHostFree(host);
+  }
+};
+}  // namespace
+
+int BatchCore::Save(const char* path) {
+  if (!path) return PMDFC_ERR_ARG;
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t st) {
+        uint64_t need = 0;
+        rc = pmdfc_cceh_snapshot(t_, nullptr, 0, &need, st);
+        if (rc != PMDFC_ERR_SIZE) {
+          set_error(std::string("Save: ") + pmdfc_last_error());
+          return;
+        }
+        MappedBuf b;
+        if (!b.alloc(need)) {
+          rc = PMDFC_ERR_NOMEM;
+          set_error("Save: no pinned host memory for the image");
+          return;
+        }
+        rc = pmdfc_cceh_snapshot(t_, b.dev, need, &need, st);
+        if (rc != PMDFC_OK) {
+          set_error(std::string("Save: ") + pmdfc_last_error());
+          return;
+        }
+        FILE* f = fopen(path, "wb");
+        const bool ok = f && fwrite(b.host, 1, need, f) == need;
+        if ((f && fclose(f) != 0) || !ok) {
+          rc = PMDFC_ERR_ARG;
+          set_error(std::string("Save: cannot write ") + path);
+        }
+      }))
+    return PMDFC_ERR_STATE;
+  return rc;
+}
+
+int BatchCore::Load(const char* path) {
+  if (!path) return PMDFC_ERR_ARG;
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t st) {
+        FILE* f = fopen(path, "rb");
+        long size = -1;
+        if (f && fseek(f, 0, SEEK_END) == 0) size = ftell(f);
+        MappedBuf b;
+        if (size <= 0 || fseek(f, 0, SEEK_SET) != 0 || !b.alloc((uint64_t)size) ||
+            fread(b.host, 1, (size_t)size, f) != (size_t)size) {
+          rc = PMDFC_ERR_ARG;
+          set_error(std::string("Load: cannot read ") + path);
+        } else {
+          rc = pmdfc_cceh_restore(t_, b.dev, (uint64_t)size, st);
+          if (rc != PMDFC_OK) set_error(std::string("Load: ") + pmdfc_last_error());
+        }
+        if (f) fclose(f);
+      }))
+    return PMDFC_ERR_STATE;
+  return rc;
+}
+
 uint64_t BatchCore::header_reloads() const {
   uint64_t n = reloads_base_.load();
   for (uint32_t g = 0; g < W_; ++g) n += ld_acq(&ctl_[g].reloads);

@@ -169,6 +169,15 @@ class BatchCore {
   // table larger than the buffers returns PMDFC_ERR_SIZE with nothing written
   int Dump(uint64_t dir_cap, uint64_t seg_cap, uint32_t* dir_canon, uint32_t* local_depth, uint64_t* prefix,
            uint64_t* keys, uint64_t* values, uint64_t* nseg_out, uint64_t* ndir_out);
+  // The table image (pmdfc_cceh_snapshot / pmdfc_cceh_restore) to and from a
+  // file of its raw bytes, through a pinned host buffer: after every op
+  // enqueued so far, the waves stopped meanwhile (they reload their header
+  // copies when the control thread starts them again).  Load replaces the
+  // whole table; an attached counting BF is neither saved nor rebuilt.
+  // PMDFC_OK or the engine's code (PMDFC_ERR_ARG also for a file that cannot
+  // be read or written); PMDFC_ERR_STATE from a completion callback.
+  int Save(const char* path);
+  int Load(const char* path);
   // chunks after which a serving wave reloaded its LDS copy of the headers
   uint64_t header_reloads() const;
   uint32_t serve_waves() const { return W_; }

@@ -93,6 +93,13 @@ class GpuCCEH : public IHash {
   size_t Capacity(void) override { return core_.Capacity(); }
   bool Recovery(void) override { return false; }  // volatile device index
 
+  // The table as a file (BatchCore::Save / Load: the image of
+  // pmdfc_cceh_snapshot): what a restarted server loads instead of replaying
+  // its inserts.  Recovery() stays the reference's repair of a crashed PMEM
+  // image, which a device table never needs.
+  bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
+  bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
+
   // ---- whole-batch entry points (host arrays, through the queue in order)
   int InsertBatch(const uint64_t* keys, const uint64_t* values, uint8_t* status, uint64_t n) {
     return core_.InsertRun(keys, values, status, n) ? PMDFC_ERR_STATE : PMDFC_OK;

@@ -76,6 +76,13 @@ class GpuCCEHHybrid : public ICCEH {
   double Utilization(void) override { return core_.Utilization(); }
   size_t Capacity(void) override { return core_.Capacity(); }
   bool Recovery(void) override { return false; }
+
+  // The table as a file (BatchCore::Save / Load: the image of
+  // pmdfc_cceh_snapshot): what a restarted server loads instead of replaying
+  // its inserts.  Recovery() stays the reference's repair of a crashed PMEM
+  // image, which a device table never needs.
+  bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
+  bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
   std::vector<unsigned> Freqs(void) override { return std::vector<unsigned>(2, 0); }
   std::vector<size_t> SegmentLoads(void) override { return std::vector<size_t>(2, 0); }
   std::vector<double> Metrics(void) override { return std::vector<double>(2, 0.0); }

@@ -151,6 +151,16 @@ int pmdfc_kv_dump(pmdfc_kv_t* kv, uint64_t dir_cap, uint64_t seg_cap, uint32_t* 
   return kv->core->Dump(dir_cap, seg_cap, dir_canon, local_depth, prefix, keys, values, nseg_out, ndir_out);
 }
 
+int pmdfc_kv_save(pmdfc_kv_t* kv, const char* path) {
+  if (!kv || !path) return PMDFC_ERR_ARG;
+  return kv->core->Save(path);
+}
+
+int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path) {
+  if (!kv || !path) return PMDFC_ERR_ARG;
+  return kv->core->Load(path);
+}
+
 int pmdfc_kv_phase(pmdfc_kv_t* kv, uint64_t* out) {
   if (!kv || !out) return PMDFC_ERR_ARG;
   const auto ph = kv->core->phase_times();

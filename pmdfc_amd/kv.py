@@ -30,7 +30,7 @@ KV_EXPORTS = [
     "pmdfc_kv_create", "pmdfc_kv_destroy", "pmdfc_kv_insert", "pmdfc_kv_get", "pmdfc_kv_ops",
     "pmdfc_kv_ops_async", "pmdfc_kv_flush", "pmdfc_kv_utilization", "pmdfc_kv_capacity",
     "pmdfc_kv_find_anyway", "pmdfc_kv_stats", "pmdfc_kv_dump", "pmdfc_kv_phase", "pmdfc_kv_last_error",
-    "pmdfc_kv_create_error",
+    "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_load",
 ]
 
 _kvlib = None
@@ -67,6 +67,8 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_dump": (i32, [P, u64, u64, P, P, P, P, P, C.POINTER(u64), C.POINTER(u64)]),
         "pmdfc_kv_create_error": (C.c_char_p, []),
         "pmdfc_kv_phase": (i32, [P, P]),
+        "pmdfc_kv_save": (i32, [P, C.c_char_p]),
+        "pmdfc_kv_load": (i32, [P, C.c_char_p]),
         "pmdfc_kv_last_error": (C.c_char_p, [P]),
     }
     for name, (res, args) in sig.items():
@@ -196,6 +198,19 @@ class KV:
         if rc != 0:
             self._err("stats", rc)
         return {n: getattr(s, n) for n, _ in Stats._fields_}
+
+    def save(self, path):
+        """The table's image (CCEH.snapshot) to a file, after every queued op."""
+        rc = load_kv_library().pmdfc_kv_save(self._h, os.fsencode(path))
+        if rc != 0:
+            self._err("save", rc)
+
+    def load(self, path):
+        """Replace the whole table with the image in a file of save() or
+        CCEH.save(); an attached counting BF is not part of the image."""
+        rc = load_kv_library().pmdfc_kv_load(self._h, os.fsencode(path))
+        if rc != 0:
+            self._err("load", rc)
 
     def phase(self) -> dict:
         a = np.zeros(NPHASE, np.uint64)
