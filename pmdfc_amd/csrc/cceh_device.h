@@ -396,7 +396,7 @@ struct DevCtl {
   uint32_t loss_events;  // splits that dropped entries (k_split, k_bucket): mixed-batch verify
   uint32_t nfin[2];      // -> k_bucket, by batch parity: buckets left for the final pass (list: fin)
   uint32_t pget;         // k_mixed_get -> bucket passes: tag of the last mixed batch that left a Get pending
-  uint32_t drop_n;       // mixed batch: entries in the drop log (k_mixed_reset zeroes it)
+  uint32_t drop_n;       // mixed batch: entries in the drop log (k_mixed_prep / k_mixed_get zero it)
   uint32_t anydecl[2];   // by batch parity: the lean first pass declined some bucket (k_apply_parked takes it)
   uint32_t ins_total;    // mixed batch in insert-set mode: its inserts (k_mixed_get_iset sums k_mixed_prep's per-block
                          // counts; k_mixed_verify's choice of how to empty the set); the join mode never sets it

@@ -200,19 +200,24 @@ struct pmdfc_cceh {
   uint32_t* pool = nullptr;   // sub-directories
   uint64_t pool_cap = 0;      // entries
   uint64_t seq = 0;             // mixed batch epoch
-  uint64_t* iset = nullptr;     // mixed: the batch's inserted keys (2^k >= 2 max_batch slots)
-  uint64_t imask = 0;
-  uint32_t* ipos = nullptr;     // mixed: per set slot, the key's insert position (valid if single)
-  uint32_t* islot = nullptr;    // mixed: per op, its insert's set slot (~0: none) -- the verify pass clears it
-  uint32_t* icnt = nullptr;     // mixed: per set slot, 1 if the key is inserted more than once
-  uint32_t* icount = nullptr;   // mixed: per 256-op block, its inserts (k_mixed_prep / k_mixed_get), summed into the host's
-                                // mode hint and, in insert-set mode, ctl->ins_total (k_mixed_get_iset / k_mixed_join)
-  uint32_t* jbits = nullptr;    // mixed: the joining Gets' filter, one per set replica (kJoinWords)
-  uint64_t last_mixed_n = 0;    // mixed: the last batch's size (with the pinned insert count: mixed_join_mode)
-  uint8_t* early = nullptr;     // mixed: per op, 1 early single-copy hit, 2 linked to its insert
-  uint32_t* elink = nullptr;    // mixed: per op, the linked insert's position (early 2) or the
-                                // pre-batch segment's local depth (early 1)
-  uint32_t* loss0 = nullptr;    // mixed: ctl->loss_events before the batch
+  // the mixed batches' device state (what fill_mixed_launch hands the kernels)
+  struct Mixed {
+    uint64_t* iset = nullptr;     // the batch's inserted keys (2^k >= 2 max_batch slots)
+    uint64_t imask = 0;
+    uint32_t* ipos = nullptr;     // per set slot, the key's insert position (valid if single)
+    uint32_t* islot = nullptr;    // per op, its insert's set slot (~0: none) -- the verify pass clears it
+    uint32_t* icnt = nullptr;     // per set slot, 1 if the key is inserted more than once
+    uint32_t* icount = nullptr;   // per 256-op block, its inserts (k_mixed_prep / k_mixed_get), summed into the host's
+                                  // mode hint and, in insert-set mode, ctl->ins_total (k_mixed_get_iset / k_mixed_join)
+    uint32_t* jbits = nullptr;    // the joining Gets' filter, one per set replica (kJoinWords)
+    uint8_t* early = nullptr;     // per op, 1 early single-copy hit, 2 linked to its insert
+    uint32_t* elink = nullptr;    // per op, the linked insert's position (early 2) or the
+                                  // pre-batch segment's local depth (early 1)
+    uint32_t* loss0 = nullptr;    // ctl->loss_events before the batch
+    ulonglong2* drops = nullptr;  // the drop log (kDropLog entries)
+    uint64_t last_n = 0;          // the last batch's size (with the pinned insert count: mixed_join_mode)
+    bool iset_dirty = false;      // a batch's prep ran without its verify pass (an error return)
+  } mx;
 
   DevCtl* ctl = nullptr;
   DevCtl* hctl = nullptr;  // pinned mirror (stats / dump only)
@@ -230,7 +235,6 @@ struct pmdfc_cceh {
   // split rounds: requests per bucket, grants, the sharded request lists
   uint2* req = nullptr;
   uint32_t* reqop = nullptr;  // batch position of each request's insert (the drop log's trigger)
-  ulonglong2* drops = nullptr;  // mixed batches: the drop log (kDropLog entries)
   uint32_t* need = nullptr;
   uint32_t* gbase = nullptr;
   uint32_t* ngrant = nullptr;
@@ -264,7 +268,6 @@ struct pmdfc_cceh {
   hipEvent_t ev_gpart[2] = {}, ev_gdone[2] = {};  // pipe_group: a group's partitions / passes done
   hipEvent_t ev_minld = nullptr;  // the last rebucket_now depth copy
   bool minld_pending = false;
-  bool iset_dirty = false;        // a mixed batch's prep ran without its verify pass (an error return)
 
   uint64_t batches = 0;
   uint64_t last_get_n = 0, last_get_blocks = 0;
@@ -489,10 +492,19 @@ static uint64_t ramp_batch(const pmdfc_cceh* t, uint64_t n) {
 
 // empty the mixed batches' key set (32 MB of fills at 1M-op batches, ~20 us)
 static int clear_key_set(pmdfc_cceh* t, hipStream_t s) {
-  HIPCHK(hipMemsetAsync(t->iset, 0xFF, (t->imask + 1) * sizeof(uint64_t), s));
-  HIPCHK(hipMemsetAsync(t->icnt, 0, (t->imask + 1) * sizeof(uint32_t), s));
-  HIPCHK(hipMemsetAsync(t->ipos, 0xFF, (t->imask + 1) * sizeof(uint32_t), s));
-  HIPCHK(hipMemsetAsync(t->jbits, 0, kJoinWords * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(t->mx.iset, 0xFF, (t->mx.imask + 1) * sizeof(uint64_t), s));
+  HIPCHK(hipMemsetAsync(t->mx.icnt, 0, (t->mx.imask + 1) * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(t->mx.ipos, 0xFF, (t->mx.imask + 1) * sizeof(uint32_t), s));
+  HIPCHK(hipMemsetAsync(t->mx.jbits, 0, kJoinWords * sizeof(uint32_t), s));
+  return PMDFC_OK;
+}
+
+// A mixed batch begins: the set is empty (emptied here if an earlier batch
+// stopped between its prep and verify passes) and counts as in use until this
+// batch's verify pass is enqueued.
+static int open_key_set(pmdfc_cceh* t, hipStream_t s) {
+  if (int rc = t->mx.iset_dirty ? clear_key_set(t, s) : PMDFC_OK) return rc;
+  t->mx.iset_dirty = true;
   return PMDFC_OK;
 }
 
@@ -511,9 +523,9 @@ static int start_host_state(pmdfc_cceh* t, hipStream_t s, uint32_t p1, uint32_t 
   // is not known empty (a new engine, or a batch that stopped between its prep
   // and verify passes): then emptied here (a cost the bench's reset at
   // every step must not pay)
-  if (t->iset_dirty) {
+  if (t->mx.iset_dirty) {
     if (int rc = clear_key_set(t, s)) return rc;
-    t->iset_dirty = false;
+    t->mx.iset_dirty = false;
   }
   t->p1 = p1;
   t->clean_sbb = ~0u;
@@ -659,6 +671,49 @@ static void fill_part_launch(const pmdfc_cceh* t, const BatchPlan& b, PartArgs& 
   a.stamps = b.stamps ? b.stamps + stamp_part_off(t) : nullptr;
 }
 
+// The mixed pre-pass and verify kernels' arguments for one general mixed batch
+// of epoch tag, by the join or by the insert set.
+static void fill_mixed_launch(const pmdfc_cceh* t, MixedArgs& a, const uint8_t* ops, const uint64_t* keys,
+                              const uint64_t* vin, uint64_t* vout, uint8_t* st, uint64_t n, uint32_t tag, bool join) {
+  const pmdfc_cceh::Mixed& m = t->mx;
+  a.ops = ops;
+  a.keys = keys;
+  a.vin = vin;
+  a.st = st;
+  a.vout = vout;
+  a.n = n;
+  a.g = t->geo();
+  a.pairs = t->pairs;
+  a.iset = m.iset;
+  a.imask = m.imask;
+  a.ipos = m.ipos;
+  a.icnt = m.icnt;
+  a.islot = m.islot;
+  a.icount = m.icount;
+  a.jbits = m.jbits;
+  a.early = m.early;
+  a.elink = m.elink;
+  a.ctl = t->ctl;
+  a.loss0 = m.loss0;
+  a.drops = m.drops;
+  a.tag = tag;
+  a.ups = t->upsert ? 1u : 0u;
+  a.hint_ins = t->d_hint + kHintMixIns;
+  a.join = join ? 1u : 0u;
+}
+
+// k_part's view of that batch: what resolves its joining Gets
+static void fill_part_join(PartArgs& p, const MixedArgs& a) {
+  p.iset = a.iset;
+  p.imask = a.imask;
+  p.icnt = a.icnt;
+  p.ipos = a.ipos;
+  p.early = a.early;
+  p.elink = a.elink;
+  p.ctl = a.ctl;
+  p.tag = a.tag;
+}
+
 // The bucket passes of one insert / mixed batch, all on the stream: a first
 // apply pass, then kSplitRounds x {split round, apply pass over the parked
 // ops (it commits the round's splits first)}, then the final pass for
@@ -790,16 +845,16 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
     // joining Gets' filter (jbits) is replicated, kJoinReps times.
     uint64_t isl = 8192;
     while (isl < 2 * (uint64_t)t->max_batch) isl <<= 1;
-    t->imask = isl - 1;
-    ALLOC(t->iset, isl * sizeof(uint64_t));
-    ALLOC(t->ipos, isl * sizeof(uint32_t));
-    ALLOC(t->icnt, isl * sizeof(uint32_t));
-    ALLOC(t->early, t->max_batch);
-    ALLOC(t->islot, t->max_batch * sizeof(uint32_t));
-    ALLOC(t->icount, (t->max_batch / 256 + 1) * sizeof(uint32_t));
-    ALLOC(t->jbits, kJoinWords * sizeof(uint32_t));
-    ALLOC(t->elink, t->max_batch * sizeof(uint32_t));
-    ALLOC(t->loss0, 256);
+    t->mx.imask = isl - 1;
+    ALLOC(t->mx.iset, isl * sizeof(uint64_t));
+    ALLOC(t->mx.ipos, isl * sizeof(uint32_t));
+    ALLOC(t->mx.icnt, isl * sizeof(uint32_t));
+    ALLOC(t->mx.early, t->max_batch);
+    ALLOC(t->mx.islot, t->max_batch * sizeof(uint32_t));
+    ALLOC(t->mx.icount, (t->max_batch / 256 + 1) * sizeof(uint32_t));
+    ALLOC(t->mx.jbits, kJoinWords * sizeof(uint32_t));
+    ALLOC(t->mx.elink, t->max_batch * sizeof(uint32_t));
+    ALLOC(t->mx.loss0, 256);
   }
   if (t->upsert) ALLOC(t->upos, (uint64_t)t->max_batch * sizeof(uint16_t));
   ALLOC(t->hdr, nb * sizeof(uint64_t));
@@ -821,7 +876,7 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   ALLOC(t->gflat_bits, sizeof(uint32_t));
   ALLOC(t->req, nb * kSplitCap * sizeof(uint2));
   ALLOC(t->reqop, nb * kSplitCap * sizeof(uint32_t));
-  ALLOC(t->drops, (uint64_t)kDropLog * sizeof(ulonglong2));
+  ALLOC(t->mx.drops, (uint64_t)kDropLog * sizeof(ulonglong2));
   // bucket w requests in shard w % 8, at most kSplitCap splits
   t->gcap = (uint32_t)((nb + kGShards - 1) / kGShards) * kSplitCap;
   ALLOC(t->gsh, 2 * kGShards * kGStride * sizeof(uint64_t));
@@ -883,7 +938,7 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
     pmdfc_cceh_destroy(t);
     return fail(PMDFC_ERR_NOMEM, "hipHostMalloc", e);
   }
-  t->iset_dirty = true;  // (fresh allocations: init_state empties the key set)
+  t->mx.iset_dirty = true;  // (fresh allocations: init_state empties the key set)
   int rc = init_state(t, (hipStream_t)0);
   if (rc == PMDFC_OK && hipStreamSynchronize((hipStream_t)0) != hipSuccess) rc = fail(PMDFC_ERR_HIP, "init");
   if (rc) {
@@ -1242,60 +1297,47 @@ int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint6
 // cheaper insert set (cceh_kernels.hip).  The count is a hint the device
 // leaves in pinned memory, read without a sync: either mode is exact.
 // PMDFC_MIXED_JOIN=0 / 1 forces one (A/B, tests).
-static bool mixed_join_mode(pmdfc_cceh* t, uint64_t n) {
+static bool mixed_join_mode(const pmdfc_cceh* t) {
   const int force = process_knobs().mixed_join;
   if (force >= 0) return force != 0;
-  (void)n;
   const uint64_t last = __atomic_load_n(t->h_hint + kHintMixIns, __ATOMIC_RELAXED);
-  return t->last_mixed_n && last * 8 > t->last_mixed_n;
+  return t->mx.last_n && last * 8 > t->mx.last_n;
 }
 
+// One general mixed batch: plan, fill, the two pre-pass launches in the chosen
+// mode's order, partition, bucket passes, verify.
 static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                      uint64_t* vout, uint8_t* st, uint64_t n, hipStream_t s) {
-  const uint64_t seq = ++t->seq;
-  // an earlier batch stopped between its prep and verify passes: start the set empty
-  if (int rc = t->iset_dirty ? clear_key_set(t, s) : PMDFC_OK) return rc;
-  t->iset_dirty = true;  // (until the verify pass that empties the set is enqueued)
+  const uint32_t tag = (uint32_t)++t->seq;
+  if (int rc = open_key_set(t, s)) return rc;
   const BatchPlan b = plan_batch(t, false, n);
   if (int rc = zero_stale_cursors(t, b, s)) return rc;
-  // statuses + early answers + the joining Gets (k_mixed_get), then the
-  // inserts' side of the join (k_mixed_join, timed as the pre-pass class);
-  // k_part resolves the joining Gets
-  const uint32_t tag = (uint32_t)seq;
-  const bool join = mixed_join_mode(t, n);
-  uint32_t* const hint_ins = t->d_hint + kHintMixIns;
-  if (join) {
+  MixedArgs M{};
+  fill_mixed_launch(t, M, ops, keys, vin, vout, st, n, tag, mixed_join_mode(t));
+  if (M.join) {
+    // statuses + early answers + the joining Gets (k_mixed_get), then the
+    // inserts' side of the join (k_mixed_join, timed as the pre-pass class);
+    // k_part resolves the joining Gets
     t->timing.begin(PMDFC_K_MIXED_GET, s);
-    launch_mixed_get(ops, keys, st, vout, n, t->geo(), t->pairs, t->early, t->islot, t->jbits, t->ctl, t->loss0, tag,
-                     t->icount, t->upsert ? 1u : 0u, s);
+    launch_mixed_get(M, s);
     t->timing.begin(PMDFC_K_PREP, s);
-    launch_mixed_join(ops, keys, st, n, t->iset, t->imask, t->ipos, t->icnt, t->islot, t->jbits, t->ctl, tag,
-                      t->icount, hint_ins, s);
+    launch_mixed_join(M, s);
   } else {
     t->timing.begin(PMDFC_K_PREP, s);
-    launch_mixed_prep(ops, keys, st, vout, n, t->geo(), t->iset, t->imask, t->ipos, t->icnt, t->early, t->islot,
-                      t->ctl, t->loss0, t->icount, s);
+    launch_mixed_prep(M, s);
     t->timing.begin(PMDFC_K_MIXED_GET, s);
-    launch_mixed_get_iset(ops, keys, st, vout, n, t->geo(), t->pairs, t->iset, t->imask, t->ipos, t->icnt, t->early,
-                          t->elink, t->ctl, tag, t->icount, t->upsert ? 1u : 0u, hint_ins, s);
+    launch_mixed_get_iset(M, s);
   }
-  t->last_mixed_n = n;
+  t->mx.last_n = n;
   PartArgs P{};
   fill_part_launch(t, b, P, ops, keys, vin, 1, st, n);
-  P.iset = t->iset;
-  P.imask = t->imask;
-  P.icnt = t->icnt;
-  P.ipos = t->ipos;
-  P.early = t->early;
-  P.elink = t->elink;
-  P.ctl = t->ctl;
-  P.tag = tag;
+  fill_part_join(P, M);
   P.vout = vout;
   BucketLaunch B{};
   fill_bucket_launch(t, b, B, n, st, vout, true);
   // when k_mixed_get answered every Get, the insert-only apply passes run
   // (upsert batches always take the mixed ones)
-  B.a.gate_tag = t->upsert ? 0u : tag;
+  B.a.gate_tag = M.ups ? 0u : tag;
   // the mixed passes on small grids unless a mixed batch of the last 64 ran
   // them (the word may lag the batches in flight: either grid is exact)
   B.a.mseen = t->d_hint + kHintMixed;
@@ -1304,17 +1346,16 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
     // (PMDFC_MIXED_SMALL=0: always on full grids)
     B.mixed_small = (last != 0 && tag - last < 64u) || !process_knobs().mixed_small ? 0u : 1u;
   }
-  B.a.drops = t->drops;  // splits log what they drop, for k_mixed_verify
+  B.a.drops = M.drops;  // splits log what they drop, for k_mixed_verify
   t->timing.begin(PMDFC_K_ROUTE, s);
-  if (t->upsert) launch_upsert_probe(keys, 1, ops, n, t->geo(), t->pairs, t->upos, s);
+  if (M.ups) launch_upsert_probe(keys, 1, ops, n, M.g, M.pairs, t->upos, s);
   launch_part(P, s);
   run_bucket_passes(t, B, s);
-  launch_mixed_verify(ops, keys, vin, st, vout, n, t->geo(), t->pairs, t->early, t->elink, t->ctl, t->loss0, t->drops,
-                      t->iset, t->icnt, t->ipos, t->islot, t->imask, join ? t->jbits : nullptr, s);
+  launch_mixed_verify(M, s);
   t->timing.end(s);
   finish_batch(t, b, kPathGeneral);
   HIPCHK(hipGetLastError());
-  t->iset_dirty = false;
+  t->mx.iset_dirty = false;  // (the verify pass that empties the set is enqueued)
   return PMDFC_OK;
 }
 

@@ -22,30 +22,49 @@ void launch_get(bool count, const uint64_t* keys, uint64_t* vout, uint8_t* st, u
 // single-copy hit, 2 linked to its insert (elink), 3 a non-wrapping
 // single-copy hit.  A Get left pending sets ctl->pget = tag.  hint_ins:
 // host-mapped, the batch's insert count (the host's choice of the next mode).
-void launch_mixed_prep(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                       uint64_t n, Geo g, uint64_t* iset, uint64_t imask, uint32_t* ipos, uint32_t* icnt,
-                       uint8_t* early, uint32_t* islot, DevCtl* ctl, uint32_t* loss0, uint32_t* icount,
-                       hipStream_t s);
-void launch_mixed_get_iset(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                           uint64_t n, Geo g, const ulonglong2* pairs, const uint64_t* iset, uint64_t imask,
-                           const uint32_t* ipos, const uint32_t* icnt, uint8_t* early, uint32_t* elink, DevCtl* ctl,
-                           uint32_t tag, uint32_t* icount, uint32_t ups, uint32_t* hint_ins, hipStream_t s);
-void launch_mixed_get(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                      uint64_t n, Geo g, const ulonglong2* pairs, uint8_t* early, uint32_t* islot, uint32_t* jbits,
-                      DevCtl* ctl, uint32_t* loss0, uint32_t tag, uint32_t* icount, uint32_t ups, hipStream_t s);
-void launch_mixed_join(const uint8_t* ops, const uint64_t* keys, const uint8_t* st, uint64_t n,
-                       uint64_t* iset, uint64_t imask, uint32_t* ipos, uint32_t* icnt, uint32_t* islot,
-                       const uint32_t* jbits, DevCtl* ctl, uint32_t tag, const uint32_t* icount, uint32_t* hint_ins,
-                       hipStream_t s);
+// The five kernels take one argument struct by value; the engine fills it once
+// per batch (cceh_engine.hip fill_mixed_launch), the launchers add only the
+// kernel or template instance, the grid and the n == 0 return.
+struct MixedArgs {
+  // the batch
+  const uint8_t* ops;
+  const uint64_t* keys;
+  const uint64_t* vin;   // (the verify pass: a linked Get takes its insert's value)
+  uint8_t* st;
+  uint64_t* vout;
+  uint64_t n;
+  // the table view
+  Geo g;
+  const ulonglong2* pairs;
+  // the key set and the join filter
+  uint64_t* iset;        // the batch's inserted keys (insert set) or joined keys (join), open addressing
+  uint64_t imask;        // its slots - 1
+  uint32_t* ipos;        // per set slot: the key's first insert position (~0 in an empty slot)
+  uint32_t* icnt;        // per set slot: insert set, 1 if inserted more than once; join, the key's inserts
+  uint32_t* islot;       // per op: its insert's set slot (~0: none), what the verify pass empties
+  uint32_t* icount;      // per 256-op block: its pending inserts
+  uint32_t* jbits;       // the joining Gets' filter (kJoinWords, kJoinReps replicas)
+  // the early answers
+  uint8_t* early;        // per op: 0 none, 1 / 3 a single-copy hit, 2 linked to its insert
+  uint32_t* elink;       // per op: the linked insert's position (early 2)
+  // the control words
+  DevCtl* ctl;
+  uint32_t* loss0;       // ctl->loss_events before the batch
+  ulonglong2* drops;     // the drop log (cceh_device.h kDropLog)
+  // the scalars
+  uint32_t tag;          // the batch's epoch, never 0 (ctl->pget, ctl->njoin)
+  uint32_t ups;          // last-writer-wins Insert: every hit depends on the batch's inserts of its key
+  uint32_t* hint_ins;    // host-mapped: the batch's insert count, or null
+  uint32_t join;         // this batch goes by the join (else by the insert set)
+};
+void launch_mixed_prep(const MixedArgs& a, hipStream_t s);
+void launch_mixed_get_iset(const MixedArgs& a, hipStream_t s);
+void launch_mixed_get(const MixedArgs& a, hipStream_t s);
+void launch_mixed_join(const MixedArgs& a, hipStream_t s);
 // after the batch: linked Gets take their insert's outcome; early hits whose
 // key a split of the batch dropped are placed before / after that split's
 // insert through the drop log (PMDFC_ST_SPLIT_LOST only if the log overflowed)
-void launch_mixed_verify(const uint8_t* ops, const uint64_t* keys, const uint64_t* vin, uint8_t* st, uint64_t* vout,
-                         uint64_t n, Geo g,
-                         const ulonglong2* pairs, const uint8_t* early, const uint32_t* elink, DevCtl* ctl,
-                         const uint32_t* loss0, const ulonglong2* drops, uint64_t* iset, uint32_t* icnt,
-                         uint32_t* ipos, const uint32_t* islot, uint64_t imask, uint32_t* jbits /* null: insert set */,
-                         hipStream_t s);
+void launch_mixed_verify(const MixedArgs& a, hipStream_t s);
 // upsert batches: pre-batch slot of each Insert's key (0xFFFF absent); ops may
 // be null (insert-only), kvs = u64 words from one key to the next
 void launch_upsert_probe(const uint64_t* keys, uint32_t kvs, const uint8_t* ops, uint64_t n, Geo g,

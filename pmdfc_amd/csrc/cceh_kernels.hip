@@ -191,7 +191,7 @@ constexpr uint32_t kBulkClearShift = PMDFC_BULK_CLEAR_SHIFT;
 constexpr uint32_t kWrapLine = (kSlots - kWindow) / 4 + 1;  // home lines >= this: the window wraps
 
 // ---- mixed batches, two exact ways to tell a Get whether the batch inserts
-// its key (the host picks one per batch, pmdfc_cceh.mixed_join):
+// its key (the host picks one per batch, cceh_engine.hip mixed_join_mode):
 //   * the INSERT set (k_mixed_prep + k_mixed_get_iset): every insert of the
 //     batch puts its key into a device-wide set (a CAS each), and the Gets that
 //     need it probe the set -- cheap when the batch inserts little (config 3:
@@ -206,157 +206,118 @@ constexpr uint32_t kWrapLine = (kSlots - kWindow) / 4 + 1;  // home lines >= thi
 // pass cleared the slots it used, islot); each op's early flag starts at 0,
 // and thread 0 opens the batch's drop log.  Each block counts its inserts
 // (icount) for the verify pass's choice of how to empty the set.
-__global__ __launch_bounds__(256) void k_mixed_prep(const uint8_t* __restrict__ ops,
-                                                    const uint64_t* __restrict__ keys,
-                                                    uint8_t* __restrict__ st,
-                                                    uint64_t* __restrict__ vout, uint64_t n, Geo g,
-                                                    uint64_t* __restrict__ iset, uint64_t imask,
-                                                    uint32_t* __restrict__ ipos,
-                                                    uint32_t* __restrict__ icnt, uint8_t* __restrict__ early,
-                                                    uint32_t* __restrict__ islot, DevCtl* __restrict__ ctl,
-                                                    uint32_t* __restrict__ loss0, uint32_t* __restrict__ icount) {
+__global__ __launch_bounds__(256) void k_mixed_prep(const MixedArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (i == 0) {
-    *loss0 = ctl->loss_events;
-    ctl->drop_n = 0;  // the batch's drop log starts empty
+    *a.loss0 = a.ctl->loss_events;
+    a.ctl->drop_n = 0;  // the batch's drop log starts empty
   }
   __shared__ uint32_t s_ins;
   if (threadIdx.x == 0) s_ins = 0;
   __syncthreads();
-  if (i < n) {
-  const uint64_t key = keys[i];
+  if (i < a.n) {
+  const uint64_t key = a.keys[i];
   const uint64_t h = hash64(key);
   uint8_t s = kStPending;
   if (reserved_key(key)) s = 3;
-  else if (wrong_shard(h, g.sbits, g.shard)) s = 8;
-  st[i] = s;
-  vout[i] = 0;
-  early[i] = 0;
+  else if (wrong_shard(h, a.g.sbits, a.g.shard)) s = 8;
+  a.st[i] = s;
+  a.vout[i] = 0;
+  a.early[i] = 0;
   uint32_t my = 0xFFFFFFFFu;
-  const bool ins = s == kStPending && ops[i] == 1;
+  const bool ins = s == kStPending && a.ops[i] == 1;
   if (ins) {
-    for (uint64_t sl = iset_slot(h, imask);; sl = (sl + 1) & imask) {
-      const uint64_t prev = atomicCAS((unsigned long long*)&iset[sl], (unsigned long long)kInvalid,
+    for (uint64_t sl = iset_slot(h, a.imask);; sl = (sl + 1) & a.imask) {
+      const uint64_t prev = atomicCAS((unsigned long long*)&a.iset[sl], (unsigned long long)kInvalid,
                                       (unsigned long long)key);
       if (prev == kInvalid) {  // the only insert of this key so far: its position
-        ipos[sl] = (uint32_t)i;
+        a.ipos[sl] = (uint32_t)i;
         my = (uint32_t)sl;
         break;
       }
       if (prev == key) {  // inserted more than once in this batch
-        icnt[sl] = 1u;
+        a.icnt[sl] = 1u;
         my = (uint32_t)sl;
         break;
       }
     }
   }
-  islot[i] = my;
+  a.islot[i] = my;
   const uint64_t b = __ballot(ins);
   if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&s_ins, (uint32_t)__popcll(b));
   }
   __syncthreads();
-  if (threadIdx.x == 0) icount[blockIdx.x] = s_ins;  // (k_mixed_get sums them into ctl->ins_total)
+  if (threadIdx.x == 0) a.icount[blockIdx.x] = s_ins;  // (k_mixed_get_iset sums them into ctl->ins_total)
 }
 
-// Early answers of a mixed batch's Gets, against the pre-batch image.  A Get
-// of a key the batch never inserts keeps its pre-batch answer wherever it
-// sits in the batch: inserts of other keys only take free slots, and splits
-// move entries without changing what a probe returns for a key with one copy.
-// A miss stays a miss (nothing adds the key); a single-copy hit keeps its
-// value unless a split of this batch drops it (CCEH_hybrid.cpp:24-27,
-// split_loss) -- k_mixed_verify checks that.  Keys with several copies (a
-// split may reorder them) stay pending.
+// ---- Early answers of a mixed batch's Gets, against the pre-batch image
+// (k_mixed_get_iset, k_mixed_get).  A Get of a key the batch never inserts
+// keeps its pre-batch answer wherever it sits in the batch: inserts of other
+// keys only take free slots, and splits move entries without changing what a
+// probe returns for a key with one copy.  A miss stays a miss (nothing adds
+// the key); a single-copy hit keeps its value unless a split of this batch
+// drops it (CCEH_hybrid.cpp:24-27, split_loss) -- k_mixed_verify checks that.
+// Keys with several copies (a split may reorder them) stay pending.
 //   A single-copy hit whose window does not wrap (home line < kWrapLine) is
-// answered WITHOUT the inserted-key set (early 3), even if the batch inserts
-// the key again: every slot of a window before a stored entry, in probe
-// order, is occupied (an entry is placed at the first free slot, by Insert
-// and by Split's replay alike, and nothing is ever deleted), so a new copy
-// lands after the old one; and a split replays a non-wrapping window in slot
-// order = probe order, placing every entry at the first free slot, so two
-// copies keep their order (the later one's slot is past the earlier one's)
-// and a dropped copy drops every later copy too.  The pre-batch copy stays
-// the first copy in probe order -- the reference's Get -- until a split of
-// the batch drops it; k_mixed_verify places those drops through the drop log
-// (and only then looks at the batch's inserts of the key).  A wrapping window
-// (y >= 996) can be replayed out of probe order, and last-writer-wins inserts
-// overwrite: those hits probe the set as before.
-//   A key the batch inserts exactly once, absent before the batch: if the
-// insert comes after this Get the key is still absent (miss now); if before,
-// the Get returns that insert's value if it was stored (resolved after the
-// batch, kStLinked).  Anything else (copies before the batch, several
-// inserts) stays pending, and the batch's ordered bucket passes answer it;
-// ctl->pget = tag tells them a Get is left (else the insert-only passes run).
+// answered WITHOUT asking whether the batch inserts the key again (early 3):
+// every slot of a window before a stored entry, in probe order, is occupied
+// (an entry is placed at the first free slot, by Insert and by Split's replay
+// alike, and nothing is ever deleted), so a new copy lands after the old one;
+// and a split replays a non-wrapping window in slot order = probe order,
+// placing every entry at the first free slot, so two copies keep their order
+// (the later one's slot is past the earlier one's) and a dropped copy drops
+// every later copy too.  The pre-batch copy stays the first copy in probe
+// order -- the reference's Get -- until a split of the batch drops it;
+// k_mixed_verify places those drops through the drop log (and only then looks
+// at the batch's inserts of the key).
+//   The other Gets -- a hit in a wrapping window (y >= 996: a split can replay
+// it out of probe order), a hit under last-writer-wins (an insert overwrites),
+// a miss -- depend on whether the batch inserts their key: each mode finds
+// that out its own way (below).  A Get left pending is answered by the
+// batch's ordered bucket passes; ctl->pget = tag tells them one is left (else
+// the insert-only passes run).
 //   A 256-thread block takes 256 consecutive ops: their pending Gets are
 // compacted in LDS and its 64 quads take them round-robin, up to kMgU each,
-// every quad's key, directory and first window-line loads (and the first
-// set slots of the Gets that need the set up front) issued back to back for
-// kMgU of them at a time (the inserts cost no quad); a miss that skipped
-// the set up front probes it after its window.
+// every quad's key, directory and first window-line loads issued back to
+// back for kMgU of them at a time (the inserts cost no quad).
 
-template <int kMgU>
-__global__ __launch_bounds__(256) void k_mixed_get_iset(const uint8_t* __restrict__ ops,
-                                                   const uint64_t* __restrict__ keys,
-                                                   uint8_t* __restrict__ st,
-                                                   uint64_t* __restrict__ vout, uint64_t n, Geo g,
-                                                   const ulonglong2* __restrict__ pairs,
-                                                   const uint64_t* __restrict__ iset,
-                                                   uint64_t imask, const uint32_t* __restrict__ ipos,
-                                                   const uint32_t* __restrict__ icnt,
-                                                   uint8_t* __restrict__ early,
-                                                   uint32_t* __restrict__ elink, DevCtl* __restrict__ ctl,
-                                                   uint32_t tag, uint32_t* __restrict__ icount, uint32_t ups,
-                                                   uint32_t* __restrict__ hint_ins) {
-  __shared__ uint8_t s_list[256];
-  __shared__ uint64_t s_key[256];
-  __shared__ uint32_t s_cnt;
+// The block's pending Gets, compacted into LDS: s_list[x] the x-th one's
+// thread (its op: the block's first + s_list[x]), s_key[x] its key, *s_cnt how
+// many.  Every thread of the block, between the barrier after *s_cnt = 0 and
+// the one before the list is read: its op is a pending Get of key k0, or not.
+__device__ __forceinline__ void list_pending_get(uint8_t* s_list, uint64_t* s_key, uint32_t* s_cnt, bool isget,
+                                                 uint64_t k0) {
   const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t base = (uint64_t)blockIdx.x * 256u;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
-  {
-    // the block's keys are read with its statuses (coalesced, one round trip)
-    // and the pending Gets' keys kept in LDS
-    const uint64_t i = base + threadIdx.x;
-    const bool in = i < n;
-    const uint8_t s0 = in ? st[i] : 0, o0 = in ? ops[i] : 1;
-    const uint64_t k0 = in ? keys[i] : kInvalid;
-    const bool isget = s0 == kStPending && o0 != 1;
-    const uint64_t bal = __ballot(isget);
-    uint32_t wb = 0;
-    if (lane == 0 && bal) wb = atomicAdd(&s_cnt, (uint32_t)__popcll(bal));
-    wb = (uint32_t)__shfl((int)wb, 0);
-    if (isget) {
-      const uint32_t x = wb + (uint32_t)__popcll(bal & ((1ULL << lane) - 1));
-      s_list[x] = (uint8_t)threadIdx.x;
-      s_key[x] = k0;
-    }
+  const uint64_t bal = __ballot(isget);
+  uint32_t wb = 0;
+  if (lane == 0 && bal) wb = atomicAdd(s_cnt, (uint32_t)__popcll(bal));
+  wb = (uint32_t)__shfl((int)wb, 0);
+  if (isget) {
+    const uint32_t x = wb + (uint32_t)__popcll(bal & ((1ULL << lane) - 1));
+    s_list[x] = (uint8_t)threadIdx.x;
+    s_key[x] = k0;
   }
-  if (blockIdx.x == 0) {  // the batch's inserts, for k_mixed_verify (block-uniform)
-    __shared__ uint32_t s_sum[4];
-    const uint32_t nblk = (uint32_t)((n + 255) / 256);
-    uint32_t c = 0;
-#pragma unroll 4
-    for (uint32_t j = threadIdx.x; j < nblk; j += 256u) c += icount[j];
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_down((int)c, o);
-    if (lane == 0) s_sum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint32_t tot = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-      ctl->ins_total = tot;
-      // the batch's inserts for the host's choice of the next batch's mode
-      // (a system-scope vector store into coherent pinned memory)
-      if (hint_ins) __hip_atomic_store(hint_ins, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-  __syncthreads();
-  const uint32_t ng = s_cnt;
-  const uint32_t quad = threadIdx.x >> 2, q = threadIdx.x & 3u, qbase = lane & ~3u;
-  bool pending = false;
-  for (uint32_t g0 = 0; g0 < 4u && quad + 64u * g0 < ng; g0 += (uint32_t)kMgU) {
-  uint64_t op[kMgU], key[kMgU], h[kMgU], iv[kMgU], iv1[kMgU], sl0[kMgU];
-  uint32_t seg[kMgU], ld[kMgU];
-  bool live[kMgU], pre[kMgU];
-  ulonglong2 p[kMgU], p2[kMgU];
+}
+
+// Mixed batches read the bucketed directory (pmdfc_cceh::geo has no flat
+// copy).  Saying so at compile time drops dir_entry's flat branch, and with it
+// a uniform load that a struct's unqualified pointers do not let the compiler
+// prove unclobbered by the kernel's own stores.
+__device__ __forceinline__ Geo bucketed(Geo g) {
+  g.flat = nullptr;
+  return g;
+}
+
+// A quad's next kMgU Gets, entries quad + 64 (g0 + u) of the ng listed, their
+// loads staged kMgU at a time: here op (base: the block's first op) and key
+// from LDS, then hash and directory entry (seg); window_lines is the third
+// stage.
+template <int kMgU>
+__device__ __forceinline__ void stage_gets(const uint8_t* s_list, const uint64_t* s_key, uint32_t ng, const MixedArgs& a,
+                                           uint64_t base, uint32_t g0, bool (&live)[kMgU], uint64_t (&op)[kMgU],
+                                           uint64_t (&key)[kMgU], uint64_t (&h)[kMgU], uint32_t (&seg)[kMgU]) {
+  const uint32_t quad = threadIdx.x >> 2;
+  const Geo g = bucketed(a.g);
 #pragma unroll
   for (int u = 0; u < kMgU; ++u) {
     const uint32_t idx = quad + 64u * (g0 + (uint32_t)u);
@@ -367,64 +328,139 @@ __global__ __launch_bounds__(256) void k_mixed_get_iset(const uint8_t* __restric
 #pragma unroll
   for (int u = 0; u < kMgU; ++u) {
     h[u] = hash64(key[u]);
-    const uint32_t e = live[u] ? dir_entry(g, h[u]) : 0u;
-    seg[u] = de_seg(e);
-    ld[u] = de_ld(e);
+    seg[u] = de_seg(live[u] ? dir_entry(g, h[u]) : 0u);
   }
+}
+// One Get's home line p (l0, in segment seg) and the window's second line p2.
+// An even home line's 128-B HBM line holds the second line too (k_get_u):
+// loaded with it, so the copy count continues without a dependent round trip
+// (odd: p2 stays invalid).
+__device__ __forceinline__ void window_lines(const ulonglong2* seg, uint32_t l0, uint32_t q, bool live,
+                                             ulonglong2& p, ulonglong2& p2) {
+  const ulonglong2* sp = seg + l0 * 4u + q;
+  p = live ? sp[0] : make_ulonglong2(kInvalid, 0);
+  p2 = live && !(l0 & 1u) ? sp[4] : make_ulonglong2(kInvalid, 0);
+}
+
+// Copies of the key in its window, from the lines window_lines loaded (pp,
+// pn): what quad_probe_once tells (0, 1, 2 for several; val: the first copy's
+// value, on every lane of the quad), but not that probe: past the preloaded
+// lines it goes on one line per round trip, not two -- few Gets get there,
+// so the loop stays rolled.
+struct WindowCopies {
+  uint32_t copies;
+  uint64_t val;
+};
+__device__ __forceinline__ WindowCopies window_copies(const ulonglong2* seg, uint64_t key, uint32_t line0,
+                                                      uint32_t q, ulonglong2 pp, ulonglong2 pn) {
+  const uint32_t qbase = (threadIdx.x & 63u) & ~3u;
+  WindowCopies w{0, 0};
+  bool have2 = !(line0 & 1u);  // pn holds the second line
+#pragma nounroll
+  for (uint32_t t = 0;;) {
+    const uint32_t mn = (uint32_t)(__ballot(pp.x == key) >> qbase) & 0xFu;
+    const uint32_t en = (uint32_t)(__ballot(pp.x == kInvalid) >> qbase) & 0xFu;
+    if (mn && w.copies == 0) w.val = shfl64(pp.y, (int)(qbase + (uint32_t)__builtin_ctz(mn)));
+    w.copies += (uint32_t)__builtin_popcount(mn);
+    if (en || w.copies > 1 || ++t == kLines) break;
+    if (have2) pp = pn;
+    else pp = seg[((line0 + t) & 255u) * 4u + q];
+    have2 = false;
+  }
+  if (w.copies > 2) w.copies = 2;
+  return w;
+}
+
+// a non-wrapping single-copy hit stands whatever the batch inserts (above)
+__device__ __forceinline__ void answer_unchecked_hit(const MixedArgs& a, uint64_t o, uint64_t val) {
+  a.vout[o] = val;
+  a.st[o] = 1;
+  a.early[o] = 3;
+}
+
+// Block 0, every thread: the batch's pending inserts, summed over the blocks'
+// counts, for the host's choice of the next batch's mode (a system-scope
+// vector store into coherent pinned memory) and, in insert-set mode, for
+// k_mixed_verify's choice of how to empty the set (ctl->ins_total).
+__device__ __forceinline__ void sum_inserts(const MixedArgs& a, bool total) {
+  __shared__ uint32_t s_sum[4];
+  const uint32_t nblk = (uint32_t)((a.n + 255) / 256);
+  uint32_t c = 0;
+#pragma unroll 4
+  for (uint32_t j = threadIdx.x; j < nblk; j += 256u) c += a.icount[j];
+  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_down((int)c, o);
+  if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t tot = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    if (total) a.ctl->ins_total = tot;
+    if (a.hint_ins) __hip_atomic_store(a.hint_ins, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The INSERT set's Gets, after k_mixed_prep set every status and filled the
+// set.  The Gets that depend on the batch's inserts of their key probe the
+// set: a hit that needs it (a wrapping window, or last-writer-wins) loads its
+// first two set slots up front, with its window lines; a miss probes it after
+// its window.
+//   A key the batch inserts exactly once, absent before the batch: if the
+// insert comes after this Get the key is still absent (miss now); if before,
+// the Get returns that insert's value if it was stored (resolved after the
+// batch, kStLinked).  Anything else (copies before the batch, several
+// inserts) stays pending.
+template <int kMgU>
+__global__ __launch_bounds__(256) void k_mixed_get_iset(const MixedArgs a) {
+  __shared__ uint8_t s_list[256];
+  __shared__ uint64_t s_key[256];
+  __shared__ uint32_t s_cnt;
+  const uint64_t base = (uint64_t)blockIdx.x * 256u;  // the block's first op
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  {
+    // the block's keys are read with its statuses (coalesced, one round trip)
+    const uint64_t i = base + threadIdx.x;
+    const bool in = i < a.n;
+    const uint8_t s0 = in ? a.st[i] : 0, o0 = in ? a.ops[i] : 1;
+    const uint64_t k0 = in ? a.keys[i] : kInvalid;
+    list_pending_get(s_list, s_key, &s_cnt, s0 == kStPending && o0 != 1, k0);
+  }
+  if (blockIdx.x == 0) sum_inserts(a, true);  // (block-uniform)
+  __syncthreads();
+  const uint32_t ng = s_cnt, quad = threadIdx.x >> 2, q = threadIdx.x & 3u;
+  bool pending = false;
+  for (uint32_t g0 = 0; g0 < 4u && quad + 64u * g0 < ng; g0 += (uint32_t)kMgU) {
+  uint64_t op[kMgU], key[kMgU], h[kMgU], iv[kMgU], iv1[kMgU], sl0[kMgU];
+  uint32_t seg[kMgU];
+  bool live[kMgU], pre[kMgU];
+  ulonglong2 p[kMgU], p2[kMgU];
+  stage_gets<kMgU>(s_list, s_key, ng, a, base, g0, live, op, key, h, seg);
 #pragma unroll
   for (int u = 0; u < kMgU; ++u) {
-    sl0[u] = iset_slot(h[u], imask);
+    sl0[u] = iset_slot(h[u], a.imask);
     const uint32_t l0 = (uint32_t)(h[u] & 0xFF);
-    // the set up front only where a hit needs it (a wrapping window, or
-    // last-writer-wins); a miss probes it after its window
-    pre[u] = live[u] && (ups != 0 || l0 >= kWrapLine);
-    iv[u] = pre[u] ? iset[sl0[u]] : kInvalid;
-    iv1[u] = pre[u] ? iset[(sl0[u] + 1) & imask] : kInvalid;
-    const ulonglong2* sp = pairs + (size_t)seg[u] * kSlots + l0 * 4u + q;
-    p[u] = live[u] ? sp[0] : make_ulonglong2(kInvalid, 0);
-    // an even home line's 128-B HBM line holds the window's second line too
-    // (k_get_u): loaded with it, so the copy count continues without a
-    // dependent round trip
-    p2[u] = live[u] && !(l0 & 1u) ? sp[4] : make_ulonglong2(kInvalid, 0);
+    pre[u] = live[u] && (a.ups != 0 || l0 >= kWrapLine);
+    iv[u] = pre[u] ? a.iset[sl0[u]] : kInvalid;
+    iv1[u] = pre[u] ? a.iset[(sl0[u] + 1) & a.imask] : kInvalid;
+    window_lines(a.pairs + (size_t)seg[u] * kSlots, l0, q, live[u], p[u], p2[u]);
   }
 #pragma unroll
   for (int u = 0; u < kMgU; ++u) {
     if (!live[u]) continue;  // quad-uniform
-    // copies of the key in its window (quad_probe_once from the loaded line)
-    uint64_t val = 0;
-    uint32_t copies = 0;
-    {
-      const ulonglong2* sp = pairs + (size_t)seg[u] * kSlots;
-      const uint32_t line0 = (uint32_t)(h[u] & 0xFF);
-      ulonglong2 pp = p[u];
-      const ulonglong2 pn = p2[u];
-      for (uint32_t t = 0;;) {
-        const uint32_t mn = (uint32_t)(__ballot(pp.x == key[u]) >> qbase) & 0xFu;
-        const uint32_t en = (uint32_t)(__ballot(pp.x == kInvalid) >> qbase) & 0xFu;
-        if (mn && copies == 0) val = shfl64(pp.y, (int)(qbase + (uint32_t)__builtin_ctz(mn)));
-        copies += (uint32_t)__builtin_popcount(mn);
-        if (en || copies > 1 || ++t == kLines) break;
-        if (t == 1 && !(line0 & 1u)) pp = pn;
-        else pp = sp[((line0 + t) & 255u) * 4u + q];
-      }
-    }
-    const uint8_t c = copies == 0 ? 0 : copies == 1 ? 1 : 2;
+    const uint32_t line0 = (uint32_t)(h[u] & 0xFF);
+    const WindowCopies w = window_copies(a.pairs + (size_t)seg[u] * kSlots, key[u], line0, q, p[u], p2[u]);
+    const uint8_t c = (uint8_t)w.copies;
     const uint64_t o = op[u];
     if (!pre[u]) {
       if (c == 2) {
         pending = true;
         continue;
       }
-      if (c == 1) {  // a non-wrapping single-copy hit: no set (see above)
-        if (q == 0) {
-          vout[o] = val;
-          st[o] = 1;
-          early[o] = 3;
-        }
+      if (c == 1) {
+        if (q == 0) answer_unchecked_hit(a, o, w.val);
         continue;
       }
-      iv[u] = iset[sl0[u]];  // a miss: the set after all
-      iv1[u] = iset[(sl0[u] + 1) & imask];
+      iv[u] = a.iset[sl0[u]];  // a miss: the set after all
+      iv1[u] = a.iset[(sl0[u] + 1) & a.imask];
     }
     // the batch's inserted-key set (linear probing from the first slot)
     uint64_t sl = ~0ull;
@@ -434,131 +470,90 @@ __global__ __launch_bounds__(256) void k_mixed_get_iset(const uint8_t* __restric
         break;
       }
       if (v == kInvalid) break;
-      s1 = (s1 + 1) & imask;
-      v = t == 0 ? iv1[u] : iset[s1];
+      s1 = (s1 + 1) & a.imask;
+      v = t == 0 ? iv1[u] : a.iset[s1];
     }
     if (sl != ~0ull) {
-      if (c != 0 || icnt[sl] != 0) {
+      if (c != 0 || a.icnt[sl] != 0) {
         pending = true;
       } else if (q == 0) {
-        const uint32_t ps = ipos[sl];
+        const uint32_t ps = a.ipos[sl];
         if ((uint64_t)ps > o) {
-          vout[o] = 0;
-          st[o] = 0;
+          a.vout[o] = 0;
+          a.st[o] = 0;
         } else {
-          st[o] = kStLinked;
-          early[o] = 2;
-          elink[o] = ps;
+          a.st[o] = kStLinked;
+          a.early[o] = 2;
+          a.elink[o] = ps;
         }
       }
     } else if (c == 2) {
       pending = true;
     } else if (q == 0) {
-      vout[o] = c ? val : 0;
-      st[o] = c ? 1 : 0;
-      early[o] = c;
+      a.vout[o] = c ? w.val : 0;
+      a.st[o] = c ? 1 : 0;
+      a.early[o] = c;
     }
   }
   }
-  if (pending && q == 0) ctl->pget = tag;  // every writer stores the same word
+  if (pending && q == 0) a.ctl->pget = a.tag;  // every writer stores the same word
 }
 
-// Early answers of a mixed batch's Gets, against the pre-batch image, in the
-// batch's first kernel (it also sets every op's status: reserved key, wrong
-// shard, pending).  A Get of a key the batch never inserts keeps its
-// pre-batch answer wherever it sits in the batch: inserts of other keys only
-// take free slots, and splits move entries without changing what a probe
-// returns for a key with one copy.  A miss stays a miss (nothing adds the
-// key); a single-copy hit keeps its value unless a split of this batch drops
-// it (CCEH_hybrid.cpp:24-27, split_loss) -- k_mixed_verify checks that.  Keys
-// with several copies (a split may reorder them) stay pending.
-//   A single-copy hit whose window does not wrap (home line < kWrapLine) is
-// answered whether or not the batch inserts the key again (early 3): every
-// slot of a window before a stored entry, in probe order, is occupied (an
-// entry is placed at the first free slot, by Insert and by Split's replay
-// alike, and nothing is ever deleted), so a new copy lands after the old one;
-// and a split replays a non-wrapping window in slot order = probe order,
-// placing every entry at the first free slot, so two copies keep their order
-// and a dropped copy drops every later copy too.  The pre-batch copy stays the
-// first copy in probe order -- the reference's Get -- until a split of the
-// batch drops it; k_mixed_verify places those drops through the drop log.
-//   The other Gets -- a hit in a wrapping window (a split can replay it out of
-// probe order), a hit under last-writer-wins (an insert overwrites), a miss --
-// depend on whether the batch inserts their key.  In the JOIN they only mark
-// their key's bit in a small filter (one per XCD: kJoinReps replicas, so a
-// hot key's marks spread over 8 words; no-return atomics, nothing waits for
-// them) and leave their probe result with status kStJoin; k_mixed_join then
-// puts into the key set only the inserts whose filter bit is set (the joined
-// keys and the filter's false positives: a few thousand CASes per config-4
-// batch instead of ~500k), counting them per key with the first position,
-// and k_part resolves each kStJoin Get from the set:
+// The JOIN's Gets, in the batch's first kernel (it also sets every op's
+// status: reserved key, wrong shard, pending).  The Gets that depend on the
+// batch's inserts of their key only mark their key's bit in a small filter
+// (one per XCD: kJoinReps replicas, so a hot key's marks spread over 8 words;
+// no-return atomics, nothing waits for them) and leave their probe result
+// with status kStJoin; k_mixed_join then puts into the key set only the
+// inserts whose filter bit is set (the joined keys and the filter's false
+// positives: a few thousand CASes per config-4 batch instead of ~500k),
+// counting them per key with the first position, and k_part resolves each
+// kStJoin Get from the set:
 //   * no insert of the key: the probe result stands (early 1 for a hit);
 //   * a miss whose key the batch inserts exactly once: before the insert a
 //     miss, after it linked to the insert (kStLinked, resolved after the batch:
 //     the insert's value if it was stored);
-//   * anything else: pending, for the batch's ordered bucket passes
-//     (ctl->pget = tag: the mixed passes run instead of the insert-only ones).
-//   A 256-thread block takes 256 consecutive ops: their pending Gets are
-// compacted in LDS and its 64 quads take them round-robin, up to kMgU each,
-// every quad's key, directory and first window-line loads issued back to
-// back for kMgU of them at a time (the inserts cost no quad).
+//   * anything else: pending.
 __device__ __forceinline__ uint32_t jbit_of(uint64_t h) { return (uint32_t)(h >> 24) & (kJoinBits - 1u); }
 
 template <int kMgU>
-__global__ __launch_bounds__(256) void k_mixed_get(const uint8_t* __restrict__ ops,
-                                                   const uint64_t* __restrict__ keys,
-                                                   uint8_t* __restrict__ st,
-                                                   uint64_t* __restrict__ vout, uint64_t n, Geo g,
-                                                   const ulonglong2* __restrict__ pairs,
-                                                   uint8_t* __restrict__ early, uint32_t* __restrict__ islot,
-                                                   uint32_t* __restrict__ jbits, DevCtl* __restrict__ ctl,
-                                                   uint32_t* __restrict__ loss0, uint32_t tag,
-                                                   uint32_t* __restrict__ icount, uint32_t ups) {
+__global__ __launch_bounds__(256) void k_mixed_get(const MixedArgs a) {
   __shared__ uint8_t s_list[256];
   __shared__ uint64_t s_key[256];
   __shared__ uint32_t s_cnt, s_ins;
   const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t base = (uint64_t)blockIdx.x * 256u;
+  const uint64_t base = (uint64_t)blockIdx.x * 256u;  // the block's first op
   if (threadIdx.x == 0) {
     s_cnt = 0;
     s_ins = 0;
     if (blockIdx.x == 0) {
-      *loss0 = ctl->loss_events;
-      ctl->drop_n = 0;  // the batch's drop log starts empty
+      *a.loss0 = a.ctl->loss_events;
+      a.ctl->drop_n = 0;  // the batch's drop log starts empty
     }
   }
   __syncthreads();
   {
     // every op's status (coalesced), and the pending Gets' keys kept in LDS
     const uint64_t i = base + threadIdx.x;
-    const bool in = i < n;
-    const uint8_t o0 = in ? ops[i] : 1;
-    const uint64_t k0 = in ? keys[i] : kInvalid;
+    const bool in = i < a.n;
+    const uint8_t o0 = in ? a.ops[i] : 1;
+    const uint64_t k0 = in ? a.keys[i] : kInvalid;
     uint8_t s0 = kStPending;
     if (in) {
       const uint64_t h0 = hash64(k0);
       if (reserved_key(k0)) s0 = 3;
-      else if (wrong_shard(h0, g.sbits, g.shard)) s0 = 8;
-      st[i] = s0;
-      vout[i] = 0;
-      early[i] = 0;
-      islot[i] = 0xFFFFFFFFu;
+      else if (wrong_shard(h0, a.g.sbits, a.g.shard)) s0 = 8;
+      a.st[i] = s0;
+      a.vout[i] = 0;
+      a.early[i] = 0;
+      a.islot[i] = 0xFFFFFFFFu;
     }
-    const bool isget = in && s0 == kStPending && o0 != 1;
-    const uint64_t bal = __ballot(isget), bins = __ballot(in && s0 == kStPending && o0 == 1);
-    uint32_t wb = 0;
-    if (lane == 0 && bal) wb = atomicAdd(&s_cnt, (uint32_t)__popcll(bal));
+    list_pending_get(s_list, s_key, &s_cnt, in && s0 == kStPending && o0 != 1, k0);
+    const uint64_t bins = __ballot(in && s0 == kStPending && o0 == 1);
     if (lane == 0 && bins) atomicAdd(&s_ins, (uint32_t)__popcll(bins));
-    wb = (uint32_t)__shfl((int)wb, 0);
-    if (isget) {
-      const uint32_t x = wb + (uint32_t)__popcll(bal & ((1ULL << lane) - 1));
-      s_list[x] = (uint8_t)threadIdx.x;
-      s_key[x] = k0;
-    }
   }
   __syncthreads();
-  const uint32_t ng = s_cnt;
-  const uint32_t quad = threadIdx.x >> 2, q = threadIdx.x & 3u, qbase = lane & ~3u;
+  const uint32_t ng = s_cnt, quad = threadIdx.x >> 2, q = threadIdx.x & 3u;
   const uint32_t rep = blockIdx.x & (kJoinReps - 1u);
   bool pending = false, join = false;
   for (uint32_t g0 = 0; g0 < 4u && quad + 64u * g0 < ng; g0 += (uint32_t)kMgU) {
@@ -566,77 +561,39 @@ __global__ __launch_bounds__(256) void k_mixed_get(const uint8_t* __restrict__ o
   uint32_t seg[kMgU];
   bool live[kMgU];
   ulonglong2 p[kMgU], p2[kMgU];
+  stage_gets<kMgU>(s_list, s_key, ng, a, base, g0, live, op, key, h, seg);
 #pragma unroll
-  for (int u = 0; u < kMgU; ++u) {
-    const uint32_t idx = quad + 64u * (g0 + (uint32_t)u);
-    live[u] = idx < ng;
-    op[u] = base + (live[u] ? s_list[idx] : 0u);
-    key[u] = live[u] ? s_key[idx] : kInvalid;
-  }
-#pragma unroll
-  for (int u = 0; u < kMgU; ++u) {
-    h[u] = hash64(key[u]);
-    seg[u] = live[u] ? de_seg(dir_entry(g, h[u])) : 0u;
-  }
-#pragma unroll
-  for (int u = 0; u < kMgU; ++u) {
-    const uint32_t l0 = (uint32_t)(h[u] & 0xFF);
-    const ulonglong2* sp = pairs + (size_t)seg[u] * kSlots + l0 * 4u + q;
-    p[u] = live[u] ? sp[0] : make_ulonglong2(kInvalid, 0);
-    // an even home line's 128-B HBM line holds the window's second line too
-    // (k_get_u): loaded with it, so the copy count continues without a
-    // dependent round trip
-    p2[u] = live[u] && !(l0 & 1u) ? sp[4] : make_ulonglong2(kInvalid, 0);
-  }
+  for (int u = 0; u < kMgU; ++u)
+    window_lines(a.pairs + (size_t)seg[u] * kSlots, (uint32_t)(h[u] & 0xFF), q, live[u], p[u], p2[u]);
 #pragma unroll
   for (int u = 0; u < kMgU; ++u) {
     if (!live[u]) continue;  // quad-uniform
-    // copies of the key in its window (quad_probe_once from the loaded line)
-    uint64_t val = 0;
-    uint32_t copies = 0;
     const uint32_t line0 = (uint32_t)(h[u] & 0xFF);
-    {
-      const ulonglong2* sp = pairs + (size_t)seg[u] * kSlots;
-      ulonglong2 pp = p[u];
-      const ulonglong2 pn = p2[u];
-      for (uint32_t t = 0;;) {
-        const uint32_t mn = (uint32_t)(__ballot(pp.x == key[u]) >> qbase) & 0xFu;
-        const uint32_t en = (uint32_t)(__ballot(pp.x == kInvalid) >> qbase) & 0xFu;
-        if (mn && copies == 0) val = shfl64(pp.y, (int)(qbase + (uint32_t)__builtin_ctz(mn)));
-        copies += (uint32_t)__builtin_popcount(mn);
-        if (en || copies > 1 || ++t == kLines) break;
-        if (t == 1 && !(line0 & 1u)) pp = pn;
-        else pp = sp[((line0 + t) & 255u) * 4u + q];
-      }
-    }
+    const WindowCopies w = window_copies(a.pairs + (size_t)seg[u] * kSlots, key[u], line0, q, p[u], p2[u]);
     const uint64_t o = op[u];
-    if (copies > 1) {  // several copies: the ordered passes (st stays pending)
+    if (w.copies > 1) {  // several copies: the ordered passes (st stays pending)
       pending = true;
       continue;
     }
-    if (copies == 1 && !ups && line0 < kWrapLine) {  // a non-wrapping single-copy hit (see above)
-      if (q == 0) {
-        vout[o] = val;
-        st[o] = 1;
-        early[o] = 3;
-      }
+    if (w.copies == 1 && !a.ups && line0 < kWrapLine) {
+      if (q == 0) answer_unchecked_hit(a, o, w.val);
       continue;
     }
     // a joining Get: its probe result, its key's filter bit (no return)
     if (q == 0) {
-      vout[o] = copies ? val : 0;
-      early[o] = (uint8_t)copies;
-      st[o] = kStJoin;
+      a.vout[o] = w.copies ? w.val : 0;
+      a.early[o] = (uint8_t)w.copies;
+      a.st[o] = kStJoin;
       const uint32_t jb = jbit_of(h[u]);
-      atomicOr(&jbits[(size_t)(jb >> 5) * kJoinReps + rep], 1u << (jb & 31u));
+      atomicOr(&a.jbits[(size_t)(jb >> 5) * kJoinReps + rep], 1u << (jb & 31u));
     }
     join = true;
   }
   }
-  if (pending && q == 0) ctl->pget = tag;  // every writer stores the same word
-  if (join && q == 0) ctl->njoin = tag;
+  if (pending && q == 0) a.ctl->pget = a.tag;  // every writer stores the same word
+  if (join && q == 0) a.ctl->njoin = a.tag;
   __syncthreads();
-  if (threadIdx.x == 0) icount[blockIdx.x] = s_ins;  // (k_mixed_join sums them: the host's mode hint)
+  if (threadIdx.x == 0) a.icount[blockIdx.x] = s_ins;  // (k_mixed_join sums them: the host's mode hint)
 }
 
 // The inserts' side of the join (see k_mixed_get): a pending insert whose
@@ -645,52 +602,31 @@ __global__ __launch_bounds__(256) void k_mixed_get(const uint8_t* __restrict__ o
 // keeps the first position (ipos starts at ~0: k_mixed_verify leaves every
 // slot it empties that way).  Exits at once when no Get of the batch joined.
 // Block 0 sums the batch's inserts for the host (the next batch's mode).
-__global__ __launch_bounds__(256) void k_mixed_join(const uint8_t* __restrict__ ops,
-                                                    const uint64_t* __restrict__ keys,
-                                                    const uint8_t* __restrict__ st, uint64_t n,
-                                                    uint64_t* __restrict__ iset, uint64_t imask,
-                                                    uint32_t* __restrict__ ipos, uint32_t* __restrict__ icnt,
-                                                    uint32_t* __restrict__ islot,
-                                                    const uint32_t* __restrict__ jbits, DevCtl* __restrict__ ctl,
-                                                    uint32_t tag, const uint32_t* __restrict__ icount,
-                                                    uint32_t* __restrict__ hint_ins) {
+__global__ __launch_bounds__(256) void k_mixed_join(const MixedArgs a) {
   static_assert(kJoinReps == 8, "one 32-B filter load per key");
   // the op's loads issued with the control word's (three round trips in all:
   // these, the filter, the set)
   const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const bool in = i < n;
-  const uint8_t o0 = in ? ops[i] : 0, st0 = in ? st[i] : 0;
-  const uint64_t key = in ? keys[i] : kInvalid;
-  const bool any = ctl->njoin == tag;
-  if (blockIdx.x == 0) {
-    __shared__ uint32_t s_sum[4];
-    const uint32_t nblk = (uint32_t)((n + 255) / 256);
-    uint32_t c = 0;
-#pragma unroll 4
-    for (uint32_t j = threadIdx.x; j < nblk; j += 256u) c += icount[j];
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_down((int)c, o);
-    if ((threadIdx.x & 63u) == 0) s_sum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    // the batch's inserts (a system-scope vector store into coherent pinned memory)
-    if (threadIdx.x == 0 && hint_ins)
-      __hip_atomic_store(hint_ins, s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3], __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  const bool in = i < a.n;
+  const uint8_t o0 = in ? a.ops[i] : 0, st0 = in ? a.st[i] : 0;
+  const uint64_t key = in ? a.keys[i] : kInvalid;
+  const bool any = a.ctl->njoin == a.tag;
+  if (blockIdx.x == 0) sum_inserts(a, false);
   if (!any || !in || o0 != 1 || st0 != kStPending) return;
   const uint64_t h = hash64(key);
   const uint32_t jb = jbit_of(h);
-  const uint4* fw = reinterpret_cast<const uint4*>(jbits + (size_t)(jb >> 5) * kJoinReps);
+  const uint4* fw = reinterpret_cast<const uint4*>(a.jbits + (size_t)(jb >> 5) * kJoinReps);
   const uint4 f0 = fw[0], f1 = fw[1];
   if (!(((f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w) >> (jb & 31u)) & 1u)) return;
-  uint64_t sl = iset_slot(h, imask);
-  for (;; sl = (sl + 1) & imask) {
-    const uint64_t prev = atomicCAS((unsigned long long*)&iset[sl], (unsigned long long)kInvalid,
+  uint64_t sl = iset_slot(h, a.imask);
+  for (;; sl = (sl + 1) & a.imask) {
+    const uint64_t prev = atomicCAS((unsigned long long*)&a.iset[sl], (unsigned long long)kInvalid,
                                     (unsigned long long)key);
     if (prev == kInvalid || prev == key) break;
   }
-  islot[i] = (uint32_t)sl;
-  atomicAdd(&icnt[sl], 1u);
-  atomicMin(&ipos[sl], (uint32_t)i);
+  a.islot[i] = (uint32_t)sl;
+  atomicAdd(&a.icnt[sl], 1u);
+  atomicMin(&a.ipos[sl], (uint32_t)i);
 }
 
 // Upsert batches (PMDFC_CFG_UPSERT): the pre-batch slot of every Insert's key
@@ -772,6 +708,8 @@ void launch_upsert_probe(const uint64_t* keys, uint32_t kvs, const uint8_t* ops,
 // sees the first copy: the pre-batch value while the count never reached 0,
 // else the value of the insert that refilled it, or a miss.  (More than 64
 // such drops of one key before one Get: PMDFC_ST_SPLIT_LOST, error bit 16.)
+// (A real call: it takes the fields it reads, not the MixedArgs, which would
+// have to be spilled to scratch to be passed by reference.)
 __device__ __noinline__ void replay_unchecked_hit(const uint8_t* __restrict__ ops, const uint64_t* __restrict__ keys,
                                                   const uint64_t* __restrict__ vin, uint8_t* __restrict__ st,
                                                   uint64_t* __restrict__ vout, uint64_t o, DevCtl* __restrict__ ctl,
@@ -835,79 +773,68 @@ __device__ __noinline__ void replay_unchecked_hit(const uint8_t* __restrict__ op
   }
 }
 
-__global__ __launch_bounds__(256) void k_mixed_verify(const uint8_t* __restrict__ ops,
-                                                      const uint64_t* __restrict__ keys,
-                                                      const uint64_t* __restrict__ vin,
-                                                      uint8_t* __restrict__ st,
-                                                      uint64_t* __restrict__ vout, uint64_t n, Geo g,
-                                                      const ulonglong2* __restrict__ pairs,
-                                                      const uint8_t* __restrict__ early,
-                                                      const uint32_t* __restrict__ elink,
-                                                      DevCtl* __restrict__ ctl,
-                                                      const uint32_t* __restrict__ loss0,
-                                                      const ulonglong2* __restrict__ drops,
-                                                      uint64_t* __restrict__ iset, uint32_t* __restrict__ icnt,
-                                                      uint32_t* __restrict__ ipos,
-                                                      const uint32_t* __restrict__ islot, uint64_t imask,
-                                                      uint32_t* __restrict__ jbits) {  // (null: an insert-set batch)
+__global__ __launch_bounds__(256) void k_mixed_verify(const MixedArgs a) {
   // a thread per op; the rare re-probe (a split of this batch dropped
   // entries) is done by the whole wave, one op at a time
   const uint64_t op = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
+  // the batch's control words, read ahead of this kernel's own stores: only
+  // then are they provably unclobbered and stay scalar loads
+  const uint32_t ins_total = a.ctl->ins_total, loss_now = a.ctl->loss_events, loss_was = *a.loss0;
+  const uint32_t nd = a.ctl->drop_n, nl = min(nd, kDropLog);
   // the set and the join filter, empty again for the next mixed batch: the
   // slots of this batch's joining Gets (scattered stores), or with many of
   // them the whole set (coalesced stores: 12 B per slot against ~2 scattered
   // stores per key); the filter (1 MiB) whole whenever a Get joined
   // (ipos too, back to ~0: the join's first-position minimum starts there)
   const uint64_t nt = (uint64_t)gridDim.x * 256u;
-  if (jbits)
-    for (uint64_t x = op; x < kJoinWords; x += nt) jbits[x] = 0u;
-  if (!jbits && ctl->ins_total > (uint32_t)((imask + 1) >> kBulkClearShift)) {
-    for (uint64_t x = op; x <= imask; x += nt) {
-      iset[x] = kInvalid;
-      icnt[x] = 0u;
-      ipos[x] = 0xFFFFFFFFu;
+  if (a.join)
+    for (uint64_t x = op; x < kJoinWords; x += nt) a.jbits[x] = 0u;
+  if (!a.join && ins_total > (uint32_t)((a.imask + 1) >> kBulkClearShift)) {
+    for (uint64_t x = op; x <= a.imask; x += nt) {
+      a.iset[x] = kInvalid;
+      a.icnt[x] = 0u;
+      a.ipos[x] = 0xFFFFFFFFu;
     }
-  } else if (op < n) {
-    const uint32_t sl = islot[op];
+  } else if (op < a.n) {
+    const uint32_t sl = a.islot[op];
     if (sl != 0xFFFFFFFFu) {
-      iset[sl] = kInvalid;
-      icnt[sl] = 0u;
-      ipos[sl] = 0xFFFFFFFFu;
+      a.iset[sl] = kInvalid;
+      a.icnt[sl] = 0u;
+      a.ipos[sl] = 0xFFFFFFFFu;
     }
   }
-  const uint8_t e = op < n ? early[op] : 0;
+  const uint8_t e = op < a.n ? a.early[op] : 0;
   bool hit = e == 1;
   const uint64_t m3 = __ballot(e == 3);
   if (e == 2) {
-    const uint32_t p = elink[op];
-    hit = st[p] == 2 || st[p] == 11;  // PMDFC_ST_INSERTED, PMDFC_ST_UPDATED (upsert)
-    vout[op] = hit ? vin[p] : 0;
-    st[op] = hit ? 1 : 0;
+    const uint32_t p = a.elink[op];
+    hit = a.st[p] == 2 || a.st[p] == 11;  // PMDFC_ST_INSERTED, PMDFC_ST_UPDATED (upsert)
+    a.vout[op] = hit ? a.vin[p] : 0;
+    a.st[op] = hit ? 1 : 0;
   }
   uint64_t m = __ballot(hit);
-  if ((!m && !m3) || ctl->loss_events == *loss0) return;
+  if ((!m && !m3) || loss_now == loss_was) return;
   for (uint64_t b = m3; b; b &= b - 1)
-    replay_unchecked_hit(ops, keys, vin, st, vout, shfl64(op, __builtin_ctzll(b)), ctl, drops);
+    replay_unchecked_hit(a.ops, a.keys, a.vin, a.st, a.vout, shfl64(op, __builtin_ctzll(b)), a.ctl, a.drops);
   const uint32_t q = lane & 3u;
   while (m) {
     const int src = __builtin_ctzll(m);
     m &= m - 1;
     const uint64_t o = shfl64(op, src);
-    const uint64_t key = keys[o];
+    const uint64_t key = a.keys[o];
     const uint64_t h = hash64(key);
     uint64_t val = 0;
     uint32_t lines;
-    const uint32_t seg = de_seg(dir_entry(g, h));
+    const uint32_t seg = de_seg(dir_entry(bucketed(a.g), h));
     // (every quad probes the same key: a wave-uniform answer)
-    if (quad_probe(pairs + (size_t)seg * kSlots, key, h, q, &val, &lines) != 0) continue;
+    if (quad_probe(a.pairs + (size_t)seg * kSlots, key, h, q, &val, &lines) != 0) continue;
     // gone: find the drop in the log, 64 entries per step
-    const uint32_t nd = ctl->drop_n, nl = min(nd, kDropLog);
     uint32_t trig = 0xFFFFFFFFu;
     bool found = false;
     for (uint32_t j0 = 0; j0 < nl && !found; j0 += 64) {
       const uint32_t j = j0 + lane;
-      const ulonglong2 d = j < nl ? drops[j] : make_ulonglong2(kInvalid, 0);
+      const ulonglong2 d = j < nl ? a.drops[j] : make_ulonglong2(kInvalid, 0);
       const uint64_t mm = __ballot(d.x == key);
       if (mm) {
         found = true;
@@ -916,13 +843,13 @@ __global__ __launch_bounds__(256) void k_mixed_verify(const uint8_t* __restrict_
     }
     if (lane != 0) continue;
     if (!found) {
-      st[o] = 10;  // PMDFC_ST_SPLIT_LOST (drop log overflowed)
-      vout[o] = 0;
-      atomicOr(&ctl->err, 1u << 16);
+      a.st[o] = 10;  // PMDFC_ST_SPLIT_LOST (drop log overflowed)
+      a.vout[o] = 0;
+      atomicOr(&a.ctl->err, 1u << 16);
     } else if ((uint64_t)trig < o) {
-      st[o] = 0;  // dropped before this Get: the reference misses
-      vout[o] = 0;
-    }  // else dropped after it: the early hit stands
+      a.st[o] = 0;  // dropped before this Get: the reference misses
+      a.vout[o] = 0;
+    }  // else dropped after it: the a.early hit stands
   }
 }
 
@@ -1156,62 +1083,33 @@ void launch_get(bool count, const uint64_t* keys, uint64_t* vout, uint8_t* st, u
     hipLaunchKernelGGL(k_get<false>, GRID(n, 64), dim3(256), 0, s, keys, vout, st, n, g, pairs, partials);
 }
 
-void launch_mixed_prep(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                       uint64_t n, Geo g, uint64_t* iset, uint64_t imask, uint32_t* ipos, uint32_t* icnt,
-                       uint8_t* early, uint32_t* islot, DevCtl* ctl, uint32_t* loss0, uint32_t* icount,
-                       hipStream_t s) {
-  hipLaunchKernelGGL(k_mixed_prep, GRID(n ? n : 1, 256), dim3(256), 0, s, ops, keys, st, vout, n, g, iset, imask,
-                     ipos, icnt, early, islot, ctl, loss0, icount);
+void launch_mixed_prep(const MixedArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_mixed_prep, GRID(a.n ? a.n : 1, 256), dim3(256), 0, s, a);
 }
 
 // Gets per quad issued together: 2 (configs 4 / 3: U=4 3.91 / 5.76, U=2
 // 3.95 / 5.96, U=1 3.97 / 5.94 Gops/s); PMDFC_MG_U overrides (A/B)
-void launch_mixed_get_iset(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                           uint64_t n, Geo g, const ulonglong2* pairs, const uint64_t* iset, uint64_t imask,
-                           const uint32_t* ipos, const uint32_t* icnt, uint8_t* early, uint32_t* elink, DevCtl* ctl,
-                           uint32_t tag, uint32_t* icount, uint32_t ups, uint32_t* hint_ins, hipStream_t s) {
-  if (!n) return;
-  const int U = process_knobs().mg_u;
-#define MG(UU)                                                                                             \
-  hipLaunchKernelGGL(k_mixed_get_iset<UU>, GRID(n, 256), dim3(256), 0, s, ops, keys, st, vout, n, g, pairs, iset, \
-                     imask, ipos, icnt, early, elink, ctl, tag, icount, ups, hint_ins)
-  if (U == 1) MG(1);
-  else if (U == 2) MG(2);
-  else MG(4);
+#define MG(kernel)                                                                       \
+  switch (process_knobs().mg_u) {                                                        \
+    case 1: hipLaunchKernelGGL(kernel<1>, GRID(a.n, 256), dim3(256), 0, s, a); break;    \
+    case 2: hipLaunchKernelGGL(kernel<2>, GRID(a.n, 256), dim3(256), 0, s, a); break;    \
+    default: hipLaunchKernelGGL(kernel<4>, GRID(a.n, 256), dim3(256), 0, s, a);          \
+  }
+void launch_mixed_get_iset(const MixedArgs& a, hipStream_t s) {
+  if (a.n) MG(k_mixed_get_iset)
+}
+
+void launch_mixed_get(const MixedArgs& a, hipStream_t s) {
+  if (a.n) MG(k_mixed_get)
+}
 #undef MG
+
+void launch_mixed_join(const MixedArgs& a, hipStream_t s) {
+  if (a.n) hipLaunchKernelGGL(k_mixed_join, GRID(a.n, 256), dim3(256), 0, s, a);
 }
 
-void launch_mixed_get(const uint8_t* ops, const uint64_t* keys, uint8_t* st, uint64_t* vout,
-                      uint64_t n, Geo g, const ulonglong2* pairs, uint8_t* early, uint32_t* islot, uint32_t* jbits,
-                      DevCtl* ctl, uint32_t* loss0, uint32_t tag, uint32_t* icount, uint32_t ups, hipStream_t s) {
-  if (!n) return;
-  const int U = process_knobs().mg_u;
-#define MG(UU)                                                                                              \
-  hipLaunchKernelGGL(k_mixed_get<UU>, GRID(n, 256), dim3(256), 0, s, ops, keys, st, vout, n, g, pairs, early, \
-                     islot, jbits, ctl, loss0, tag, icount, ups)
-  if (U == 1) MG(1);
-  else if (U == 2) MG(2);
-  else MG(4);
-#undef MG
-}
-
-void launch_mixed_join(const uint8_t* ops, const uint64_t* keys, const uint8_t* st, uint64_t n,
-                       uint64_t* iset, uint64_t imask, uint32_t* ipos, uint32_t* icnt, uint32_t* islot,
-                       const uint32_t* jbits, DevCtl* ctl, uint32_t tag, const uint32_t* icount, uint32_t* hint_ins,
-                       hipStream_t s) {
-  if (n)
-    hipLaunchKernelGGL(k_mixed_join, GRID(n, 256), dim3(256), 0, s, ops, keys, st, n, iset, imask, ipos, icnt, islot,
-                       jbits, ctl, tag, icount, hint_ins);
-}
-
-void launch_mixed_verify(const uint8_t* ops, const uint64_t* keys, const uint64_t* vin, uint8_t* st, uint64_t* vout,
-                         uint64_t n, Geo g,
-                         const ulonglong2* pairs, const uint8_t* early, const uint32_t* elink, DevCtl* ctl,
-                         const uint32_t* loss0, const ulonglong2* drops, uint64_t* iset, uint32_t* icnt,
-                         uint32_t* ipos, const uint32_t* islot, uint64_t imask, uint32_t* jbits, hipStream_t s) {
-  if (n)
-    hipLaunchKernelGGL(k_mixed_verify, GRID(n, 256), dim3(256), 0, s, ops, keys, vin, st, vout, n, g, pairs, early,
-                       elink, ctl, loss0, drops, iset, icnt, ipos, islot, imask, jbits);
+void launch_mixed_verify(const MixedArgs& a, hipStream_t s) {
+  if (a.n) hipLaunchKernelGGL(k_mixed_verify, GRID(a.n, 256), dim3(256), 0, s, a);
 }
 
 void launch_init_segments(ulonglong2* pairs, uint32_t* occ, uint8_t* ldep, uint32_t* pool,

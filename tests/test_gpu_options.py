@@ -75,7 +75,7 @@ def test_optional_layouts_match_oracle(env):
 # cuttings (every op and the final table against the serial oracle), plus a
 # stream whose Gets hit wrapping windows of keys the same batch re-inserts
 # and misses of keys inserted once or twice in the batch (the join's cases).
-CHILD_MIXED = r'''
+MIXED_STREAMS = r'''
 import json, sys, numpy as np
 sys.path.insert(0, "tests")
 import scenarios as S
@@ -99,7 +99,8 @@ ops = np.concatenate(ops); keys = np.concatenate(keys)
 vals = keys ^ np.uint64(0x5555)
 scen["join_cases"] = (64, "hybrid", np.where(ops == 1, S.OP_INSERT, S.OP_GET).astype(np.uint8), keys, vals)
 out = {}
-for name in ("mixed_cap16_60k", "mixed_cap2_30k_ins80", "split_loss_mixed", "dup_wrap", "join_cases"):
+'''
+CHILD_MIXED = MIXED_STREAMS + r'''for name in ("mixed_cap16_60k", "mixed_cap2_30k_ins80", "split_loss_mixed", "dup_wrap", "join_cases"):
     init_cap, conv, ops, keys, vals = scen[name]
     n = keys.size
     for batch in (9000, 20000, 65536):
@@ -125,6 +126,45 @@ def test_mixed_modes_match_oracle(mode):
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
     assert all(res.values()), (mode, res)
+
+
+# The Get kernels of both modes have one template instance per unroll
+# (PMDFC_MG_U: Gets per quad issued together; 2 is the default the test above
+# runs).  The other two, each under both modes: the join's stream and
+# dup_wrap, cut into 9,000-op batches -- the smallest that still take the
+# general path (PMDFC_MEDIUM_MAX is 8,192) -- with first-writer-wins and with
+# last-writer-wins inserts (under upsert every hit asks about the batch's
+# inserts of its key).  Every op and the final table against the serial oracle.
+CHILD_MIXED_UNROLL = MIXED_STREAMS + r'''for name in ("join_cases", "dup_wrap"):
+    init_cap, conv, ops, keys, vals = scen[name]
+    n = keys.size
+    batch = 9000
+    for upsert in (False, True):
+        t = P.CCEH(init_cap, convention=conv, max_batch=batch, max_segments=16384, upsert=upsert)
+        o = O.OracleCCEH(t.initial_depth, upsert=upsert)
+        vo, st = t.MixedBatches(ops, keys, vals, list(range(0, n, batch)) + [n])
+        ov, ost = o.mixed(ops, keys, vals)
+        ok = bool(np.array_equal(st, ost) and np.array_equal(vo, ov))
+        d, od = t.dump(), o.dump()
+        ok = ok and d["depth"] == od["depth"] and all(np.array_equal(d[f], od[f]) for f in ("local_depth", "keys", "values"))
+        ok = ok and t.stats()["error_flags"] == 0
+        out[f"{name}/upsert={upsert}"] = ok
+        t.close()
+print(json.dumps(out))
+'''
+
+
+@pytest.mark.parametrize("mode", ["0", "1"])
+@pytest.mark.parametrize("unroll", ["1", "4"])
+def test_mixed_get_unrolls_match_oracle(unroll, mode):
+    e = dict(os.environ)
+    e["PMDFC_MG_U"] = unroll
+    e["PMDFC_MIXED_JOIN"] = mode
+    r = subprocess.run([sys.executable, "-c", CHILD_MIXED_UNROLL], cwd=REPO, env=e, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(res) == 4 and all(res.values()), (unroll, mode, res)
 
 
 # The routed call forced through its pack / exchange / unpack on one rank
