@@ -29,8 +29,19 @@ class Stats(C.Structure):
 def build() -> str:
     path = os.path.join(_HERE, "liboracle.so")
     src = os.path.join(_HERE, "cceh_oracle.c")
-    if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-s", "-C", _HERE, "liboracle.so"])
+    def stale():
+        return not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src)
+
+    if stale():
+        # Processes that start together (the spawned ranks of tests/test_dist_gloo.py,
+        # when theirs is the first use of the oracle) must not all rebuild, nor load a
+        # library another is still writing: one makes it under the lock (the Makefile
+        # moves the finished file into place), the others wait and find it fresh.
+        import fcntl
+        with open(os.path.join(_HERE, ".liboracle.lock"), "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            if stale():
+                subprocess.check_call(["make", "-s", "-C", _HERE, "liboracle.so"])
     return path
 
 

@@ -393,6 +393,74 @@ def scenarios(hash64):
     return s
 
 
+# Probe shapes of a pure Get (get_probe_shapes): where in its 8-line window a
+# Get stops.  GET_SHAPE_DEPTH is the table's initial depth (8 segments, the
+# segment of a key is h >> 61); nothing splits.
+GET_SHAPE_DEPTH = 3
+GET_SHAPE_STAIR_OFF = (0, 1, 5)  # segments 0..2: home line 8 i + off holds i + 1 keys, i = 0..31
+GET_SHAPE_RANDOM = 420           # segment 3: random keys, overlapping windows
+# segments 4..7: one partly filled wrapping window each, (home line, keys): a
+# miss stops on line keys // 4 + 1 of the window: past line 255 for the first
+# three, on line 255 for the last
+GET_SHAPE_WRAP_PARTIAL = ((254, 10), (255, 18), (253, 26), (250, 22))
+GET_SHAPE_WRAP_LINE = 249        # home lines from here on: the window wraps past line 255
+
+
+def get_probe_shapes(hash64):
+    """A table and a query set that stop Gets on every line of the window, as
+    (initial_depth, insert_keys, values, query_keys), inserts and queries
+    shuffled.  CCEH_hybrid at depth 3, no split: an insert takes the first free
+    slot of its window, so the keys of one home line fill its lines in order.
+      segments 0, 1, 2  staircases: home line 8 i + off (off = 0, 1, 5) holds
+                        i + 1 keys, i = 0..31.  The windows of one staircase
+                        never overlap: key j of a home line is a hit on line
+                        j // 4 + 1, an absent key of that line misses on line
+                        (i + 1) // 4 + 1, or after all 8 lines when i = 31.
+                        off = 0: even home lines (the second line is loaded
+                        with the first); off = 1, 5: odd ones, and the wrapping
+                        home lines 249 and 253;
+      segment 3         420 random keys: windows that overlap;
+      segments 4..7     GET_SHAPE_WRAP_PARTIAL: wrapping windows filled up to
+                        line 255 or a line past it, so a miss stops there.
+    Queries: every inserted key, 3 absent keys per crafted home line (and of
+    the empty wrapping home line 251 of segment 4), 1000 absent keys of
+    segment 3, the two reserved keys, 40 keys a second time."""
+    rng = np.random.default_rng(20261020)
+    pool = np.unique(rng.integers(1, 1 << 62, 600000, dtype=np.uint64))
+    h = hash64(pool)
+    seg = (h >> np.uint64(64 - GET_SHAPE_DEPTH)).astype(np.int64)
+    cell = seg * 256 + (h & np.uint64(0xFF)).astype(np.int64)
+    order = np.argsort(cell, kind="stable")
+    pool = pool[order]
+    start = np.searchsorted(cell[order], np.arange(256 * (1 << GET_SHAPE_DEPTH) + 1))
+
+    def take(s, line, n, skip=0):
+        a = int(start[s * 256 + line]) + skip
+        if a + n > int(start[s * 256 + line + 1]):
+            raise ValueError(f"key pool too small for segment {s}, line {line}")
+        return pool[a:a + n]
+
+    ins, absent = [], []
+    for s, off in enumerate(GET_SHAPE_STAIR_OFF):
+        for i in range(32):
+            ins.append(take(s, 8 * i + off, i + 1))
+            absent.append(take(s, 8 * i + off, 3, skip=i + 1))
+    s3 = pool[int(start[3 * 256]):int(start[4 * 256])]
+    s3 = s3[rng.permutation(s3.size)]
+    ins.append(s3[:GET_SHAPE_RANDOM])
+    absent.append(s3[GET_SHAPE_RANDOM:GET_SHAPE_RANDOM + 1000])
+    for j, (line, n) in enumerate(GET_SHAPE_WRAP_PARTIAL):
+        ins.append(take(4 + j, line, n))
+        absent.append(take(4 + j, line, 3, skip=n))
+    absent.append(take(4, 251, 3))
+    ins = np.concatenate(ins)
+    ins = ins[rng.permutation(ins.size)]
+    absent = np.concatenate(absent)
+    q = np.concatenate([ins, absent, np.array([2**64 - 1, 2**64 - 2], np.uint64), ins[:30], absent[:10]])
+    q = q[rng.permutation(q.size)]
+    return GET_SHAPE_DEPTH, ins, _vals(ins, 0x6E7), q
+
+
 # CCEH::FindAnyway fixtures (tests/golden/findany.json): scenarios whose
 # final table the reference scans for these queries
 FINDANY_CASES = ["dup_wrap", "dup32", "split_loss", "cap2_ins3k", "mixed_cap2_30k_ins80", "src_cap2m_ins50k"]
