@@ -14,8 +14,9 @@ HOSTHDRS := pmdfc_amd/host/batch_core.h pmdfc_amd/host/gpu_cceh.h pmdfc_amd/host
 KVTEST := $(LIBDIR)/test_gpu_kv
 FRONTBENCH := $(LIBDIR)/bench_frontend
 IMGKVTEST := $(LIBDIR)/test_gpu_image_kv
+BFKVTEST := $(LIBDIR)/test_gpu_filter_kv
 
-all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(FRONTBENCH) oracle
+all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(FRONTBENCH) oracle
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -32,6 +33,9 @@ $(KVTEST): tests/cpp/test_gpu_kv.cpp $(HOSTLIB)
 
 $(IMGKVTEST): tests/cpp/test_gpu_image_kv.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_image_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
+
+$(BFKVTEST): tests/cpp/test_gpu_filter_kv.cpp $(HOSTLIB)
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_filter_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(FRONTBENCH): tools/bench_frontend.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tools/bench_frontend.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'

@@ -539,6 +539,34 @@ int pmdfc_cbf_export(pmdfc_cbf_t* f, pmdfc_bloom_t* b, void* stream);
 int pmdfc_cbf_counters(pmdfc_cbf_t* f, uint8_t** d_counters, uint64_t** d_bitmap, uint64_t* nwords);
 int pmdfc_cbf_get_counters_host(pmdfc_cbf_t* f, uint8_t* host, uint64_t nbits);
 int pmdfc_cbf_get_bitmap_host(pmdfc_cbf_t* f, uint64_t* host, uint64_t nwords);
+/* The filter from the table: one device pass over the stored
+ * keys of t -- every slot whose key != INVALID, the slots the image of
+ * pmdfc_cceh_snapshot holds -- counting each as Insert does.  Afterwards the
+ * counters are those of CountingBloomFilter after Insert(key) once per stored
+ * copy of every key in t (increments saturate at 255, so no order matters),
+ * starting from a cleared filter (counters and packed bitmap, as
+ * pmdfc_cbf_clear) or, with PMDFC_CBF_KEEP, added to what f holds (several
+ * tables into one filter: the shards of one server on one GPU).  The packed
+ * bitmap is not refreshed: call pmdfc_cbf_pack.  *d_stored (nullable, a
+ * device u64) receives the stored entries, the image header's live entries.
+ * Against a filter maintained by pmdfc_cbf_insert beside the inserts, the
+ * rebuilt one
+ *   - no longer counts the entries a split dropped (stats.split_loss),
+ *   - counts extent heads, which KV::InsertExtent (server/KV.cpp:129-143)
+ *     never counts: a superset, so still no false negative,
+ *   - counts a key overwritten in upsert mode once, not once per Insert;
+ * on a duplicate-free stream with no drops and no extents the two are
+ * byte-identical.
+ * Both calls enqueue on `stream` and never synchronise, like insert and get,
+ * so they follow the batches already queued there.  f and t on one device
+ * (else PMDFC_ERR_ARG).  Like snapshot, they read the whole table: they must
+ * not run beside serving waves (stop them first). */
+#define PMDFC_CBF_KEEP 1u /* do not clear first: add this table's keys to what f holds */
+int pmdfc_cbf_rebuild(pmdfc_cbf_t* f, pmdfc_cceh_t* t, uint32_t flags, uint64_t* d_stored, void* stream);
+/* Query of every stored key of t: d_out2 (two device u64) = {stored entries,
+ * stored entries whose Query is false} -- the second is what a client that
+ * probes this filter's bitmap would never ask the server for.  f is unchanged. */
+int pmdfc_cbf_audit(pmdfc_cbf_t* f, pmdfc_cceh_t* t, uint64_t* d_out2, void* stream);
 
 /* ---- extents ------------------------------------------
  * convention 0 = CCEH_hybrid: Insert_extent(key, value, len)

@@ -96,10 +96,26 @@ int pmdfc_kv_dump(pmdfc_kv_t* kv, uint64_t dir_cap, uint64_t seg_cap, uint32_t* 
 /* The table image (pmdfc_cceh.h, snapshot and restore) as a file of its raw
  * bytes, after every queued op, the serving waves stopped meanwhile.  load
  * replaces the whole table with the file's; the refusals are those of the
- * restore call, plus PMDFC_ERR_ARG for a file that cannot be read or written.  An
- * attached counting BF is neither saved nor rebuilt. */
+ * restore call, plus PMDFC_ERR_ARG for a file that cannot be read or written.
+ * The counting BF is not in the file, because it follows from the table:
+ * after a successful load an attached filter (pmdfc_kv_attach_cbf) is rebuilt
+ * from the loaded table and packed, under the same stop of the waves, so the
+ * next bitmap shipped to a client admits every restored key; a refused file
+ * leaves the filter as it was.  save is the same with or without a filter. */
 int pmdfc_kv_save(pmdfc_kv_t* kv, const char* path);
 int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path);
+/* KV's server counting BF (server/KV.cpp:113-121): from now on every Insert
+ * also counts in f (pmdfc_cbf_create, same device; it must outlive its use
+ * here); f == NULL detaches.  After every queued op. */
+int pmdfc_kv_attach_cbf(pmdfc_kv_t* kv, pmdfc_cbf_t* f);
+/* The attached filter from the table, after every queued op and with the
+ * serving waves stopped: pmdfc_cbf_rebuild (cleared first; its header comment
+ * says how the result differs from the maintained filter), pmdfc_cbf_pack, one
+ * wait.  *stored (nullable): the table's stored entries.  pmdfc_kv_audit_cbf:
+ * pmdfc_cbf_audit, out2 = {stored entries, those whose Query is false}.
+ * PMDFC_ERR_STATE without an attached filter. */
+int pmdfc_kv_rebuild_cbf(pmdfc_kv_t* kv, uint64_t* stored);
+int pmdfc_kv_audit_cbf(pmdfc_kv_t* kv, uint64_t* out2);
 /* counters: [0] serving-wave launches, [1] device chunks (wave chunks +
  * flood batches), [2] flood batches, [3] ops in flood batches, [4] failed
  * ops, [5] ops completed, [6] serving waves per launch, [7] header reloads

@@ -21,6 +21,9 @@
 //           set on the device) the subtractions are added back (u32 add/sub
 //           commute, borrows included) and one wave replays the batch in
 //           order.  No host synchronisation either way.
+//   Rebuild / audit (no reference counterpart: its Delete is a stub, so its
+//           filter only drifts): k_cbf_scan visits every stored key of a
+//           table, Insert or Query each (pmdfc_cbf_rebuild, pmdfc_cbf_audit).
 #include "cceh_device.h"
 #include "cceh_kernels.h"
 
@@ -42,16 +45,9 @@ __device__ __forceinline__ uint32_t load_agent(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Insert x n: lane per key, the k indices computed first so the k CAS chains
-// are independent and overlap.  ops != nullptr: only keys whose op is
-// PMDFC_OP_INSERT (1) count (KV::Insert's bf->Insert, server/KV.cpp:113-114).
-__global__ __launch_bounds__(256) void k_cbf_insert(uint8_t* __restrict__ cnt, uint64_t m,
-                                                    uint32_t k, const uint64_t* __restrict__ keys,
-                                                    const uint8_t* __restrict__ ops, uint64_t n) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  if (ops && ops[i] != 1) return;
-  const uint64_t key = keys[i];
+// Insert of one key: the k indices computed first (four at a time), so the
+// CAS chains are independent and overlap.
+__device__ __forceinline__ void cbf_add_key(uint8_t* __restrict__ cnt, uint64_t m, uint32_t k, uint64_t key) {
   for (uint32_t j0 = 0; j0 < k; j0 += 4) {
     uint32_t* w[4];
     uint32_t sh[4], old[4];
@@ -77,6 +73,17 @@ __global__ __launch_bounds__(256) void k_cbf_insert(uint8_t* __restrict__ cnt, u
       }
     }
   }
+}
+
+// Insert x n: lane per key.  ops != nullptr: only keys whose op is
+// PMDFC_OP_INSERT (1) count (KV::Insert's bf->Insert, server/KV.cpp:113-114).
+__global__ __launch_bounds__(256) void k_cbf_insert(uint8_t* __restrict__ cnt, uint64_t m,
+                                                    uint32_t k, const uint64_t* __restrict__ keys,
+                                                    const uint8_t* __restrict__ ops, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  if (ops && ops[i] != 1) return;
+  cbf_add_key(cnt, m, k, keys[i]);
 }
 
 // Query x n (:133-143): lane per key, stops at the first zero counter.
@@ -196,6 +203,65 @@ __global__ __launch_bounds__(256) void k_cbf_pack(const uint8_t* __restrict__ cn
   }
 }
 
+// The scan over the stored keys (pmdfc_cbf_rebuild / pmdfc_cbf_audit): arena
+// segments [0, min(ctl->nsegs, max_segs)) -- every id below nsegs is live
+// (child 0 of a split keeps its parent's id), ids from nsegs on may hold
+// anything and are never read -- a workgroup of four waves per segment and
+// step of the grid-stride loop, 16 B per lane, the four loads of a segment
+// issued together (k_image_gather's shape) and one segment ahead of the
+// visit, so the read hides behind the counter traffic.  A slot is stored
+// iff key != INVALID (image.hip's rule).  Arena order: both visitors commute.
+//   rebuild: Insert of every stored key (cbf_add_key: saturation exact, lanes
+//            meeting in one word or byte serialise on its CAS);
+//   audit:   Query of every stored key, out[1] += the keys it fails for.
+// out[0] += the stored keys (out nullable for the rebuild): summed per wave
+// over its segments, one atomic per wave and word.
+template <bool kAudit>
+__global__ __launch_bounds__(256) void k_cbf_scan(const ulonglong2* __restrict__ pairs,
+                                                  const DevCtl* __restrict__ ctl, uint32_t max_segs,
+                                                  uint8_t* __restrict__ cnt, uint64_t m, uint32_t k,
+                                                  unsigned long long* __restrict__ out) {
+  const uint32_t nsegs = min(ctl->nsegs, max_segs);
+  uint32_t stored = 0, missing = 0;  // this lane's
+  ulonglong2 p[4], nx[4];
+  if (blockIdx.x < nsegs) {
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) p[q] = ld_pair_l2(pairs + (size_t)blockIdx.x * kSlots + q * 256u + threadIdx.x);
+  }
+  for (uint32_t sid = blockIdx.x; sid < nsegs; sid += gridDim.x) {
+    // the next segment's loads fly while this one's keys are visited
+    const uint32_t nsid = sid + gridDim.x;
+    if (nsid < nsegs) {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) nx[q] = ld_pair_l2(pairs + (size_t)nsid * kSlots + q * 256u + threadIdx.x);
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      if (p[q].x == kInvalid) continue;
+      ++stored;
+      if (kAudit) {
+        bool hit = true;
+        for (uint32_t j = 0; j < k && hit; ++j) hit = cnt[cbf_idx(p[q].x, j, m)] != 0;
+        missing += hit ? 0u : 1u;
+      } else {
+        cbf_add_key(cnt, m, k, p[q].x);
+      }
+    }
+    if (nsid < nsegs) {
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) p[q] = nx[q];
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    stored += __shfl_xor((int)stored, o);
+    if (kAudit) missing += __shfl_xor((int)missing, o);
+  }
+  if ((threadIdx.x & 63u) == 0 && out) {
+    if (stored) atomicAdd(out, (unsigned long long)stored);
+    if (kAudit && missing) atomicAdd(out + 1, (unsigned long long)missing);
+  }
+}
+
 #define GRID(n, per) dim3((unsigned)(((n) + (per)-1) / (per)))
 
 void launch_cbf_insert(uint8_t* cnt, uint64_t m, uint32_t k, const uint64_t* keys,
@@ -226,6 +292,15 @@ void launch_cbf_pack(const uint8_t* cnt, uint64_t m, uint64_t* bm, hipStream_t s
   const uint64_t nchunks = (m + kCbfChunk - 1) / kCbfChunk;
   const uint64_t blocks = std::min<uint64_t>((nchunks + 3) / 4, 4096);
   hipLaunchKernelGGL(k_cbf_pack, dim3((unsigned)blocks), dim3(256), 0, s, cnt, bm, nwords, nchunks);
+}
+
+void launch_cbf_scan(bool audit, const ulonglong2* pairs, const DevCtl* ctl, uint64_t max_segs, uint8_t* cnt,
+                     uint64_t m, uint32_t k, unsigned long long* out, hipStream_t s) {
+  const dim3 grid((unsigned)std::min<uint64_t>(std::max<uint64_t>(max_segs, 1), kCbfScanBlocks));
+  if (audit)
+    hipLaunchKernelGGL(k_cbf_scan<true>, grid, dim3(256), 0, s, pairs, ctl, (uint32_t)max_segs, cnt, m, k, out);
+  else
+    hipLaunchKernelGGL(k_cbf_scan<false>, grid, dim3(256), 0, s, pairs, ctl, (uint32_t)max_segs, cnt, m, k, out);
 }
 
 }  // namespace pmdfc

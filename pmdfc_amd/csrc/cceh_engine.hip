@@ -2315,6 +2315,37 @@ int pmdfc_cbf_get_bitmap_host(pmdfc_cbf_t* f, uint64_t* host, uint64_t nwords) {
   return PMDFC_OK;
 }
 
+int pmdfc_cbf_rebuild(pmdfc_cbf_t* f, pmdfc_cceh_t* t, uint32_t flags, uint64_t* d_stored, void* stream) {
+  if (!f || !t) return fail(PMDFC_ERR_ARG, "null argument");
+  if (f->dev != t->dev) return fail(PMDFC_ERR_ARG, "cbf and index on different devices");
+  if (flags & ~PMDFC_CBF_KEEP) return fail(PMDFC_ERR_ARG, "cbf_rebuild: unknown flags");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  if (!(flags & PMDFC_CBF_KEEP)) {
+    HIPCHK(hipMemsetAsync(f->cnt, 0, f->padded, s));
+    HIPCHK(hipMemsetAsync(f->bm, 0, f->nwords * 8, s));
+  }
+  if (d_stored) HIPCHK(hipMemsetAsync(d_stored, 0, sizeof(uint64_t), s));
+  launch_cbf_scan(false, t->pairs, t->ctl, t->max_segs, f->cnt, f->nbits, f->k,
+                  reinterpret_cast<unsigned long long*>(d_stored), s);
+  HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
+
+int pmdfc_cbf_audit(pmdfc_cbf_t* f, pmdfc_cceh_t* t, uint64_t* d_out2, void* stream) {
+  if (!f || !t || !d_out2) return fail(PMDFC_ERR_ARG, "null argument");
+  if (f->dev != t->dev) return fail(PMDFC_ERR_ARG, "cbf and index on different devices");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(d_out2, 0, 2 * sizeof(uint64_t), s));
+  launch_cbf_scan(true, t->pairs, t->ctl, t->max_segs, f->cnt, f->nbits, f->k,
+                  reinterpret_cast<unsigned long long*>(d_out2), s);
+  HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
+
 // ----------------------------------------------------------- trace ingestion
 
 int pmdfc_trace_create(int device, pmdfc_trace_t** out) {

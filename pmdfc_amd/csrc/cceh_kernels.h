@@ -421,6 +421,13 @@ void launch_cbf_query(const uint8_t* cnt, uint64_t m, uint32_t k, const uint64_t
 void launch_cbf_delete(uint8_t* cnt, uint64_t m, uint32_t k, const uint64_t* keys, uint8_t* out,
                        uint64_t n, uint32_t* flag, hipStream_t s);
 void launch_cbf_pack(const uint8_t* cnt, uint64_t m, uint64_t* bm, hipStream_t s);
+// The stored keys of arena segments [0, min(ctl->nsegs, max_segs)) (nsegs read
+// on the device): rebuild counts each into cnt, audit queries each; out[0] +=
+// the stored keys, audit: out[1] += those whose Query is false.  out is not
+// zeroed here; the rebuild takes out == null.
+constexpr uint32_t kCbfScanBlocks = 2048;  // the loop's grid: 8 workgroups of four waves per CU
+void launch_cbf_scan(bool audit, const ulonglong2* pairs, const DevCtl* ctl, uint64_t max_segs, uint8_t* cnt,
+                     uint64_t m, uint32_t k, unsigned long long* out, hipStream_t s);
 
 // trace.hip (replay_KV trace ingestion)
 struct TraceLine {

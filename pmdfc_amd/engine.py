@@ -28,6 +28,7 @@ LIB_PATH = os.environ.get("PMDFC_LIB") or os.path.join(_HERE, "lib", "libpmdfc_c
 
 OP_GET, OP_INSERT = 0, 1
 PMDFC_ERR_SIZE = -5  # an output buffer is smaller than the result (include/pmdfc_cceh.h)
+CBF_KEEP = 1  # PMDFC_CBF_KEEP: pmdfc_cbf_rebuild adds to what the filter holds
 (ST_MISS, ST_HIT, ST_INSERTED, ST_RESERVED_KEY, ST_UNSPLITTABLE, ST_DEPTH_LIMIT, ST_CAPACITY,
  ST_FILTERED, ST_WRONG_SHARD, ST_ROUTE_OVERFLOW, ST_SPLIT_LOST, ST_UPDATED) = range(12)
 CFG_UPSERT = 1  # pmdfc_cceh_config_t.flags: last-writer-wins Insert
@@ -86,6 +87,7 @@ EXPORTS = [
     "pmdfc_route_batches",
     "pmdfc_route_mixed_batches",
     "pmdfc_cceh_snapshot", "pmdfc_cceh_restore",
+    "pmdfc_cbf_rebuild", "pmdfc_cbf_audit",
 ]
 
 
@@ -164,6 +166,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_cbf_counters": (i32, [P, C.POINTER(P), C.POINTER(P), C.POINTER(u64)]),
         "pmdfc_cbf_get_counters_host": (i32, [P, P, u64]),
         "pmdfc_cbf_get_bitmap_host": (i32, [P, P, u64]),
+        "pmdfc_cbf_rebuild": (i32, [P, P, u32, P, P]),
+        "pmdfc_cbf_audit": (i32, [P, P, P, P]),
         "pmdfc_cceh_insert_extent": (i32, [P, i32, P, P, P, P, u64, C.POINTER(u64), P]),
         "pmdfc_cceh_get_extent": (i32, [P, i32, P, P, P, P, u64, P]),
         "pmdfc_trace_create": (i32, [i32, C.POINTER(P)]),
@@ -717,6 +721,26 @@ class CountingBloomFilter:
 
     def Clear(self):
         _check(load_library().pmdfc_cbf_clear(self._h, self._d.stream()), "cbf_clear")
+
+    def rebuild(self, index: "CCEH", keep: bool = False) -> int:
+        """The filter from the table: every stored key of `index` counted as
+        Insert would, after the batches already queued on the stream.  The
+        filter is cleared first unless `keep` (then the keys are added to what
+        it holds: several shards into one filter).  Returns the stored entries
+        (so it synchronises); the packed bitmap waits for ToOrdinaryBloomFilter()."""
+        out = torch.empty(1, dtype=torch.int64, device=self._d.device)
+        _check(load_library().pmdfc_cbf_rebuild(self._h, index.handle, CBF_KEEP if keep else 0, out.data_ptr(),
+                                                self._d.stream()), "cbf_rebuild")
+        return int(out.item())
+
+    def audit(self, index: "CCEH"):
+        """(stored, missing): the stored entries of `index`, and those whose
+        Query on this filter is false -- what a client probing its bitmap
+        would never ask for."""
+        out = torch.empty(2, dtype=torch.int64, device=self._d.device)
+        _check(load_library().pmdfc_cbf_audit(self._h, index.handle, out.data_ptr(), self._d.stream()), "cbf_audit")
+        stored, missing = out.tolist()
+        return stored, missing
 
     def counters(self) -> np.ndarray:
         out = np.empty(self.nbits, np.uint8)

@@ -931,6 +931,57 @@ int BatchCore::pack_counting_bf() {
   return rc;
 }
 
+// (inside with_engine) the attached filter from the table, then its bitmap:
+// two launches and one wait (fa_dev_[0]: the stored count)
+int BatchCore::rebuild_bf(void* stream, uint64_t* stored) {
+  hipStream_t s = (hipStream_t)stream;
+  uint64_t n = 0;
+  int rc = pmdfc_cbf_rebuild(bf_, t_, 0, fa_dev_, s);
+  if (rc == PMDFC_OK) rc = pmdfc_cbf_pack(bf_, s);
+  if (rc != PMDFC_OK) {
+    set_error(std::string("RebuildCountingBF: ") + pmdfc_last_error());
+    return rc;
+  }
+  if (hipMemcpyAsync(&n, fa_dev_, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    set_error("RebuildCountingBF: the device pass failed");
+    return PMDFC_ERR_HIP;
+  }
+  if (stored) *stored = n;
+  return PMDFC_OK;
+}
+
+int BatchCore::RebuildCountingBF(uint64_t* stored) {
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t s) {
+        if (bf_) rc = rebuild_bf(s, stored);
+      }))
+    return PMDFC_ERR_STATE;
+  return rc;
+}
+
+int BatchCore::AuditCountingBF(uint64_t* stored, uint64_t* missing) {
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t s) {
+        if (!bf_) return;
+        uint64_t out[2] = {0, 0};
+        rc = pmdfc_cbf_audit(bf_, t_, fa_dev_, s);
+        if (rc != PMDFC_OK) {
+          set_error(std::string("AuditCountingBF: ") + pmdfc_last_error());
+          return;
+        }
+        if (hipMemcpyAsync(out, fa_dev_, 16, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+          rc = PMDFC_ERR_HIP;
+          set_error("AuditCountingBF: the device pass failed");
+          return;
+        }
+        if (stored) *stored = out[0];
+        if (missing) *missing = out[1];
+      }))
+    return PMDFC_ERR_STATE;
+  return rc;
+}
+
 double BatchCore::Utilization() {
   double u = -1.0;
   if (!with_engine([&](hipStream_t) {
@@ -1066,6 +1117,9 @@ int BatchCore::Load(const char* path) {
         } else {
           rc = pmdfc_cceh_restore(t_, b.dev, (uint64_t)size, st);
           if (rc != PMDFC_OK) set_error(std::string("Load: ") + pmdfc_last_error());
+          // the filter follows from the table (it is not in the file); a
+          // refused image leaves it as it was
+          else if (bf_) rc = rebuild_bf(st, nullptr);
         }
         if (f) fclose(f);
       }))

@@ -39,8 +39,9 @@
 // queued and a callback runs on the control thread when its result is back.
 //
 // Calls that need the whole engine (Utilization, Capacity, FindAnyway, the
-// counting-BF pack and attach) wait for every op queued before them, stop
-// the device wave, run on the engine's stream, and start it again.
+// counting-BF pack, attach, rebuild and audit, Save and Load) wait for every
+// op queued before them, stop the device wave, run on the engine's stream,
+// and start it again.
 //
 // Errors never escape a call: a failed HIP or engine call fails the ops it
 // concerns with status kBatchFailed (0xFF) and records a sticky message
@@ -153,6 +154,15 @@ class BatchCore {
   void attach_counting_bf(pmdfc_cbf_t* f);
   // ToOrdinaryBloomFilter after the ops enqueued so far (rdma_svr.cpp:256-264)
   int pack_counting_bf();
+  // The attached filter from the table (pmdfc_cbf_rebuild, cleared first) and
+  // its packed bitmap, after the ops enqueued so far, the waves stopped
+  // meanwhile; when they start again they count into the rebuilt filter.
+  // *stored (nullable): the table's stored entries.  Without a filter
+  // PMDFC_ERR_STATE.
+  int RebuildCountingBF(uint64_t* stored = nullptr);
+  // pmdfc_cbf_audit: the stored entries, and those the attached filter's
+  // Query denies (what a client probing its bitmap would never ask for)
+  int AuditCountingBF(uint64_t* stored, uint64_t* missing);
 
   // ---- introspection (synchronous; from a completion callback they fail:
   // Utilization -1, FindAnyway kBatchFailed, Capacity 0)
@@ -173,7 +183,10 @@ class BatchCore {
   // file of its raw bytes, through a pinned host buffer: after every op
   // enqueued so far, the waves stopped meanwhile (they reload their header
   // copies when the control thread starts them again).  Load replaces the
-  // whole table; an attached counting BF is neither saved nor rebuilt.
+  // whole table.  The counting BF is not in the file, because it follows from
+  // the table: after a successful Load an attached filter is rebuilt and
+  // packed (RebuildCountingBF) under the same stop of the waves; a refused
+  // file leaves the filter as it was.
   // PMDFC_OK or the engine's code (PMDFC_ERR_ARG also for a file that cannot
   // be read or written); PMDFC_ERR_STATE from a completion callback.
   int Save(const char* path);
@@ -280,6 +293,7 @@ class BatchCore {
   bool stop_server();    // stop them and wait for them (srv_mu_ held)
   template <class F>
   bool with_engine(F f);  // flush, stop the waves, f(stream), start them again
+  int rebuild_bf(void* stream, uint64_t* stored);  // (inside with_engine) rebuild + pack + one sync
 
   pmdfc_cceh_t* t_ = nullptr;
   pmdfc_cbf_t* bf_ = nullptr;

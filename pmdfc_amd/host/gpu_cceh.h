@@ -96,7 +96,8 @@ class GpuCCEH : public IHash {
   // The table as a file (BatchCore::Save / Load: the image of
   // pmdfc_cceh_snapshot): what a restarted server loads instead of replaying
   // its inserts.  Recovery() stays the reference's repair of a crashed PMEM
-  // image, which a device table never needs.
+  // image, which a device table never needs.  Load rebuilds and packs an
+  // attached counting BF from the loaded table (the filter is not in the file).
   bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
   bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
 
@@ -112,6 +113,9 @@ class GpuCCEH : public IHash {
   // device batch also increments it, on the batch's stream
   void attach_counting_bf(pmdfc_cbf_t* f) { core_.attach_counting_bf(f); }
   int pack_counting_bf() { return core_.pack_counting_bf(); }
+  // the filter (and its bitmap) from the table as it stands: drops of splits
+  // and saturated counters no longer drift (BatchCore::RebuildCountingBF)
+  int rebuild_counting_bf(uint64_t* stored = nullptr) { return core_.RebuildCountingBF(stored); }
 
   BatchCore& core() { return core_; }
   pmdfc_cceh_t* engine() { return core_.engine(); }

@@ -80,9 +80,15 @@ class GpuCCEHHybrid : public ICCEH {
   // The table as a file (BatchCore::Save / Load: the image of
   // pmdfc_cceh_snapshot): what a restarted server loads instead of replaying
   // its inserts.  Recovery() stays the reference's repair of a crashed PMEM
-  // image, which a device table never needs.
+  // image, which a device table never needs.  Load rebuilds and packs an
+  // attached counting BF from the loaded table (the filter is not in the file).
   bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
   bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
+  // NUMA_KV keeps no filter of its own; a server that ships one per index
+  // attaches it here: every per-op Insert counts in it, extent heads do not
+  void attach_counting_bf(pmdfc_cbf_t* f) { core_.attach_counting_bf(f); }
+  int pack_counting_bf() { return core_.pack_counting_bf(); }
+  int rebuild_counting_bf(uint64_t* stored = nullptr) { return core_.RebuildCountingBF(stored); }
   std::vector<unsigned> Freqs(void) override { return std::vector<unsigned>(2, 0); }
   std::vector<size_t> SegmentLoads(void) override { return std::vector<size_t>(2, 0); }
   std::vector<double> Metrics(void) override { return std::vector<double>(2, 0.0); }

@@ -161,6 +161,22 @@ int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path) {
   return kv->core->Load(path);
 }
 
+int pmdfc_kv_attach_cbf(pmdfc_kv_t* kv, pmdfc_cbf_t* f) {
+  if (!kv) return PMDFC_ERR_ARG;
+  kv->core->attach_counting_bf(f);
+  return PMDFC_OK;
+}
+
+int pmdfc_kv_rebuild_cbf(pmdfc_kv_t* kv, uint64_t* stored) {
+  if (!kv) return PMDFC_ERR_ARG;
+  return kv->core->RebuildCountingBF(stored);
+}
+
+int pmdfc_kv_audit_cbf(pmdfc_kv_t* kv, uint64_t* out2) {
+  if (!kv || !out2) return PMDFC_ERR_ARG;
+  return kv->core->AuditCountingBF(out2, out2 + 1);
+}
+
 int pmdfc_kv_phase(pmdfc_kv_t* kv, uint64_t* out) {
   if (!kv || !out) return PMDFC_ERR_ARG;
   const auto ph = kv->core->phase_times();

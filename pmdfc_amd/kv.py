@@ -31,6 +31,7 @@ KV_EXPORTS = [
     "pmdfc_kv_ops_async", "pmdfc_kv_flush", "pmdfc_kv_utilization", "pmdfc_kv_capacity",
     "pmdfc_kv_find_anyway", "pmdfc_kv_stats", "pmdfc_kv_dump", "pmdfc_kv_phase", "pmdfc_kv_last_error",
     "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_load",
+    "pmdfc_kv_attach_cbf", "pmdfc_kv_rebuild_cbf", "pmdfc_kv_audit_cbf",
 ]
 
 _kvlib = None
@@ -69,6 +70,9 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_phase": (i32, [P, P]),
         "pmdfc_kv_save": (i32, [P, C.c_char_p]),
         "pmdfc_kv_load": (i32, [P, C.c_char_p]),
+        "pmdfc_kv_attach_cbf": (i32, [P, P]),
+        "pmdfc_kv_rebuild_cbf": (i32, [P, C.POINTER(u64)]),
+        "pmdfc_kv_audit_cbf": (i32, [P, P]),
         "pmdfc_kv_last_error": (C.c_char_p, [P]),
     }
     for name, (res, args) in sig.items():
@@ -104,12 +108,14 @@ class KV:
         if rc != 0:
             raise PmdfcError(f"pmdfc_kv_create failed ({rc}): {L.pmdfc_kv_create_error().decode()}")
         self._h = h
+        self._bf = None
         self.initial_depth = depth
 
     def close(self):
         if getattr(self, "_h", None):
             load_kv_library().pmdfc_kv_destroy(self._h)
             self._h = None
+            self._bf = None
 
     def __del__(self):
         try:
@@ -207,10 +213,38 @@ class KV:
 
     def load(self, path):
         """Replace the whole table with the image in a file of save() or
-        CCEH.save(); an attached counting BF is not part of the image."""
+        CCEH.save().  The counting BF is not part of the image: an attached
+        one is rebuilt from the loaded table and packed (rebuild_filter); a
+        refused file leaves it as it was."""
         rc = load_kv_library().pmdfc_kv_load(self._h, os.fsencode(path))
         if rc != 0:
             self._err("load", rc)
+
+    # ---- KV's server counting BF (server/KV.cpp:113-121)
+    def attach_counting_bf(self, f):
+        """Every later Insert also counts in `f` (a CountingBloomFilter on the
+        same device, kept alive here); None detaches."""
+        rc = load_kv_library().pmdfc_kv_attach_cbf(self._h, f._h if f is not None else None)
+        if rc != 0:
+            self._err("attach_cbf", rc)
+        self._bf = f
+
+    def rebuild_filter(self) -> int:
+        """The attached filter rebuilt from the table (CountingBloomFilter.rebuild)
+        and packed, after every queued op.  Returns the stored entries."""
+        n = C.c_uint64()
+        rc = load_kv_library().pmdfc_kv_rebuild_cbf(self._h, C.byref(n))
+        if rc != 0:
+            self._err("rebuild_cbf", rc)
+        return n.value
+
+    def audit_filter(self):
+        """(stored, missing) of the attached filter (CountingBloomFilter.audit)."""
+        out = (C.c_uint64 * 2)()
+        rc = load_kv_library().pmdfc_kv_audit_cbf(self._h, out)
+        if rc != 0:
+            self._err("audit_cbf", rc)
+        return out[0], out[1]
 
     def phase(self) -> dict:
         a = np.zeros(NPHASE, np.uint64)
