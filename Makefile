@@ -6,7 +6,7 @@ LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
 SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/cceh_engine.hip
-HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h include/pmdfc_cceh.h
+HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h $(CSRC)/packed_image.h include/pmdfc_cceh.h
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
 HOSTLIB := $(LIBDIR)/libpmdfc_gpucceh.so
@@ -15,8 +15,9 @@ KVTEST := $(LIBDIR)/test_gpu_kv
 FRONTBENCH := $(LIBDIR)/bench_frontend
 IMGKVTEST := $(LIBDIR)/test_gpu_image_kv
 BFKVTEST := $(LIBDIR)/test_gpu_filter_kv
+PAKKVTEST := $(LIBDIR)/test_gpu_packed_kv
 
-all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(FRONTBENCH) oracle
+all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(FRONTBENCH) oracle
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -36,6 +37,9 @@ $(IMGKVTEST): tests/cpp/test_gpu_image_kv.cpp $(HOSTLIB)
 
 $(BFKVTEST): tests/cpp/test_gpu_filter_kv.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_filter_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
+
+$(PAKKVTEST): tests/cpp/test_gpu_packed_kv.cpp $(HOSTLIB)
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_packed_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(FRONTBENCH): tools/bench_frontend.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tools/bench_frontend.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'

@@ -302,6 +302,36 @@ int pmdfc_cceh_snapshot(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t
  * runs, batches, error_flags, ...) start from zero, as after a reset. */
 int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* stream);
 
+/* ---- packed table image and entry export (synchronous) ----------------
+ * The packed image (pmdfc_amd/csrc/packed_image.h) holds only
+ * the stored pairs: the same 4,096-byte header with the magic "PMDFCPAK"
+ * (version 1), the local depths as above, then nseg x 32 occupancy words in
+ * canonical order (bit s & 31 of word s >> 5: slot s holds an entry) and the
+ * live x {key, value} pairs in canonical segment order and slot order, each
+ * region zero-padded to a multiple of 4,096 bytes.  It holds exactly what the
+ * version-1 image holds; at half load it is about half its size.
+ * pmdfc_cceh_restore takes either kind, told apart by the magic.  For a packed
+ * image the same rules hold; in addition the occupancy words must count the
+ * header's live entries and the paddings must be zero (PMDFC_ERR_ARG, the
+ * table as it was: every segment's offset into the pairs is a prefix sum of
+ * those counts, so no image can steer an access outside its buffer).  A stored
+ * key that is reserved or outside its segment's hash prefix: PMDFC_ERR_ARG,
+ * the table freshly reset, as for the version-1 image. */
+/* Same contract as pmdfc_cceh_snapshot; the size needed depends on the live
+ * entries.  PMDFC_ERR_STATE if the stored keys and the occupancy words
+ * disagree (an engine invariant; t is unchanged). */
+int pmdfc_cceh_snapshot_packed(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t* bytes_out, void* stream);
+/* The stored pairs as dense DEVICE arrays, in canonical segment order and slot
+ * order within a segment (the order of the packed image): *n_out entries.
+ * Either array may be NULL.  Both NULL or cap_entries too small:
+ * PMDFC_ERR_SIZE with *n_out set, nothing written.  t is unchanged.  Like
+ * snapshot it reads the whole table: not beside the serving waves. */
+int pmdfc_cceh_export_entries(pmdfc_cceh_t* t, uint64_t* d_keys, uint64_t* d_values, uint64_t cap_entries,
+                              uint64_t* n_out, void* stream);
+/* Segments per block of the live-count scan both calls and the packed restore
+ * run (tests cover tables of more segments than one block). */
+uint32_t pmdfc_cceh_packed_scan_block(void);
+
 /* ---- kernel timing (HIP events on the launching stream) -------------- */
 /* kernel classes */
 #define PMDFC_K_GET 0

@@ -103,6 +103,9 @@ int pmdfc_kv_dump(pmdfc_kv_t* kv, uint64_t dir_cap, uint64_t seg_cap, uint32_t* 
  * next bitmap shipped to a client admits every restored key; a refused file
  * leaves the filter as it was.  save is the same with or without a filter. */
 int pmdfc_kv_save(pmdfc_kv_t* kv, const char* path);
+/* save with the packed image (pmdfc_cceh_snapshot_packed: only the stored
+ * pairs, about half the bytes at half load); load reads either kind. */
+int pmdfc_kv_save_packed(pmdfc_kv_t* kv, const char* path);
 int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path);
 /* KV's server counting BF (server/KV.cpp:113-121): from now on every Insert
  * also counts in f (pmdfc_cbf_create, same device; it must outlive its use

@@ -34,6 +34,7 @@
 #include "cceh_device.h"
 #include "cceh_kernels.h"
 #include "image.h"
+#include "packed_image.h"
 #include "knobs.h"
 
 using namespace pmdfc;
@@ -1683,26 +1684,13 @@ int pmdfc_cceh_snapshot(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t
   return PMDFC_OK;
 }
 
-int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* stream) {
-  if (!t || !buf) return fail(PMDFC_ERR_ARG, "null argument");
-  std::lock_guard<std::mutex> lk(t->mu);
-  DevGuard g(t->dev);
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipDeviceSynchronize());
-  if ((uintptr_t)buf & 15u) return fail(PMDFC_ERR_ARG, "restore: the image must be 16-byte aligned");
-  if (bytes < image::kHeaderBytes) return fail(PMDFC_ERR_ARG, image::error_string(image::kShort));
-  const uint8_t* in = static_cast<const uint8_t*>(buf);
-  // ---- decided on the host, the table untouched: header, local depths, fit
-  std::vector<uint8_t> hb(image::kHeaderBytes);
-  HIPCHK(hipMemcpy(hb.data(), in, hb.size(), hipMemcpyDefault));
-  image::Header h;
-  if (int e = image::parse_header(hb.data(), bytes, &h)) return fail(PMDFC_ERR_ARG, image::error_string(e));
-  if (h.initial_depth != t->D0 || h.shard_bits != t->sbits || h.shard_id != t->shard)
-    return fail(PMDFC_ERR_ARG, "restore: the image's initial_depth / shard_bits / shard_id are not this engine's");
-  std::vector<uint8_t> ld(image::depth_bytes(h.nseg));
-  HIPCHK(hipMemcpy(ld.data(), in + image::kHeaderBytes, ld.size(), hipMemcpyDefault));
-  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_ARG, image::error_string(e));
-  if (h.nseg > t->max_segs) return fail(PMDFC_ERR_SIZE, "restore: the image has more segments than max_segments");
+// The part of a restore that both image kinds share, from a header and local
+// depths that validation accepted and nseg <= max_segments: the directory's
+// fit (still the table untouched), then the table becomes the image's.  `a`
+// arrives with the image's own fields set (img; for a packed image occ_img,
+// base, live).
+static int restore_table(pmdfc_cceh_t* t, hipStream_t s, const image::Header& h, const std::vector<uint8_t>& ld,
+                         ScatterArgs a) {
   const uint32_t nseg = (uint32_t)h.nseg;
   // the directory: the bucket bits rebucket_now would have reached, each
   // bucket's sub-directory as deep as its deepest segment, in its fixed slot
@@ -1749,8 +1737,6 @@ int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* s
   HIPCHK(hipMemcpy(t->hdr, hd.data(), hd.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   if (int rc = start_host_state(t, s, p1, h.min_ld)) return rc;
   launch_image_ctl(batch_words(t), t->ctl, c, t->d_hint, s);
-  ScatterArgs a{};
-  a.img = reinterpret_cast<const ulonglong2*>(in + image::pairs_offset(nseg));
   a.desc = d_desc;
   a.hdr = t->hdr;
   a.nseg = nseg;
@@ -1772,6 +1758,228 @@ int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* s
     HIPCHK(hipStreamSynchronize(s));
     return fail(PMDFC_ERR_ARG, "restore: live keys outside their segment's hash prefix (the table was reset)");
   }
+  return PMDFC_OK;
+}
+
+namespace {
+// the device scratch of launch_image_live_scan for nseg segments, and a word
+// for what a pack counts
+struct LiveWork {
+  DevTmp mem;
+  LiveScan w{};
+  uint32_t* bad = nullptr;
+  int alloc(uint32_t nseg) {
+    const uint64_t nblk = live_scan_blocks(nseg);
+    HIPCHK(hipMalloc(&mem.p, (nseg + 2 * nblk + 1) * sizeof(uint64_t) + ((uint64_t)nseg + 1) * sizeof(uint32_t)));
+    w.base = static_cast<uint64_t*>(mem.p);
+    w.sums = w.base + nseg;
+    w.offs = w.sums + nblk;
+    w.cnt = reinterpret_cast<uint32_t*>(w.offs + nblk + 1);
+    bad = w.cnt + nseg;
+    return PMDFC_OK;
+  }
+  // (after launch_image_live_scan on s) the grand total, read back
+  int total(uint32_t nseg, hipStream_t s, uint64_t* out) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, w.offs + live_scan_blocks(nseg), sizeof *out, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return PMDFC_OK;
+  }
+};
+}  // namespace
+
+// pmdfc_cceh_restore of a packed image (packed_image.h); hb: its header bytes
+static int restore_packed(pmdfc_cceh_t* t, hipStream_t s, const uint8_t* in, uint64_t bytes,
+                          const std::vector<uint8_t>& hb) {
+  // ---- the table untouched: header, local depths, the occupancy words' count
+  image::Header h;
+  if (int e = packed::parse_header(hb.data(), bytes, &h)) return fail(PMDFC_ERR_ARG, packed::error_string(e));
+  if (h.initial_depth != t->D0 || h.shard_bits != t->sbits || h.shard_id != t->shard)
+    return fail(PMDFC_ERR_ARG, "restore: the image's initial_depth / shard_bits / shard_id are not this engine's");
+  std::vector<uint8_t> ld(image::depth_bytes(h.nseg));
+  HIPCHK(hipMemcpy(ld.data(), in + image::kHeaderBytes, ld.size(), hipMemcpyDefault));
+  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_ARG, packed::error_string(e));
+  if (h.nseg > t->max_segs) return fail(PMDFC_ERR_SIZE, "restore: the image has more segments than max_segments");
+  const uint32_t nseg = (uint32_t)h.nseg;
+  // the two paddings the device pass never looks at (each under 4,096 bytes)
+  const uint64_t occ_end = packed::occ_offset(nseg) + (uint64_t)nseg * packed::kOccWords * 4;
+  const uint64_t pair_end = packed::pairs_offset(nseg) + h.live * 16;
+  std::vector<uint8_t> pad((packed::pairs_offset(nseg) - occ_end) + (h.total_bytes - pair_end));
+  if (packed::pairs_offset(nseg) > occ_end)
+    HIPCHK(hipMemcpy(pad.data(), in + occ_end, packed::pairs_offset(nseg) - occ_end, hipMemcpyDefault));
+  if (h.total_bytes > pair_end)
+    HIPCHK(hipMemcpy(pad.data() + (packed::pairs_offset(nseg) - occ_end), in + pair_end, h.total_bytes - pair_end,
+                     hipMemcpyDefault));
+  for (uint8_t b : pad)
+    if (b) return fail(PMDFC_ERR_ARG, packed::error_string(packed::kPadding));
+  // every segment's offset into the pairs is a prefix sum of popcounts: they
+  // must sum to the header's live count, which parse_header fitted to the buffer
+  const uint32_t* occ_img = reinterpret_cast<const uint32_t*>(in + packed::occ_offset(nseg));
+  LiveWork lw;
+  if (int rc = lw.alloc(nseg)) return rc;
+  launch_image_live_scan(occ_img, nullptr, 0, nseg, lw.w, s);
+  uint64_t live = 0;
+  if (int rc = lw.total(nseg, s, &live)) return rc;
+  if (live != h.live) return fail(PMDFC_ERR_ARG, packed::error_string(packed::kLive));
+  ScatterArgs a{};
+  a.img = reinterpret_cast<const ulonglong2*>(in + packed::pairs_offset(nseg));
+  a.occ_img = occ_img;
+  a.base = lw.w.base;
+  a.live = h.live;
+  return restore_table(t, s, h, ld, a);
+}
+
+int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* stream) {
+  if (!t || !buf) return fail(PMDFC_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipDeviceSynchronize());
+  if ((uintptr_t)buf & 15u) return fail(PMDFC_ERR_ARG, "restore: the image must be 16-byte aligned");
+  if (bytes < image::kHeaderBytes) return fail(PMDFC_ERR_ARG, image::error_string(image::kShort));
+  const uint8_t* in = static_cast<const uint8_t*>(buf);
+  // ---- decided on the host, the table untouched: header, local depths, fit
+  std::vector<uint8_t> hb(image::kHeaderBytes);
+  HIPCHK(hipMemcpy(hb.data(), in, hb.size(), hipMemcpyDefault));
+  if (memcmp(hb.data(), packed::kMagic, 8) == 0) return restore_packed(t, s, in, bytes, hb);
+  image::Header h;
+  if (int e = image::parse_header(hb.data(), bytes, &h)) return fail(PMDFC_ERR_ARG, image::error_string(e));
+  if (h.initial_depth != t->D0 || h.shard_bits != t->sbits || h.shard_id != t->shard)
+    return fail(PMDFC_ERR_ARG, "restore: the image's initial_depth / shard_bits / shard_id are not this engine's");
+  std::vector<uint8_t> ld(image::depth_bytes(h.nseg));
+  HIPCHK(hipMemcpy(ld.data(), in + image::kHeaderBytes, ld.size(), hipMemcpyDefault));
+  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_ARG, image::error_string(e));
+  if (h.nseg > t->max_segs) return fail(PMDFC_ERR_SIZE, "restore: the image has more segments than max_segments");
+  ScatterArgs a{};
+  a.img = reinterpret_cast<const ulonglong2*>(in + image::pairs_offset(h.nseg));
+  return restore_table(t, s, h, ld, a);
+}
+
+// ---- packed image and entry export (packed_image.h, image.hip)
+
+namespace {
+// Canonical order on the device for one synchronous call: order[i] the
+// directory entry of canonical segment i, ld[i] its local depth, and from the
+// engine's occupancy words base[i], the entries stored before segment i, and
+// their total.
+struct Canon {
+  DevTmp wk, ord;
+  LiveWork lw;
+  uint32_t nseg = 0;
+  uint32_t* order = nullptr;
+  uint8_t* ld = nullptr;
+  uint64_t live = 0;
+};
+
+int canonical_live(pmdfc_cceh_t* t, hipStream_t s, Canon& c) {
+  const uint32_t nb = 1u << t->p1;
+  HIPCHK(hipMalloc(&c.wk.p, (2ull * nb + 1) * sizeof(uint32_t)));
+  uint32_t* cnt = static_cast<uint32_t*>(c.wk.p);
+  uint32_t *base = cnt + nb, *total = base + nb;
+  launch_image_count(t->hdr, t->pool, (uint32_t)t->pool_cap, t->p1, t->sbits, cnt, base, total, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(&c.nseg, total, sizeof c.nseg, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (c.nseg == 0 || c.nseg > t->max_segs) return fail(PMDFC_ERR_STATE, "the directory walk found no sound table");
+  HIPCHK(hipMalloc(&c.ord.p, (uint64_t)c.nseg * (sizeof(uint32_t) + 1)));
+  c.order = static_cast<uint32_t*>(c.ord.p);
+  c.ld = reinterpret_cast<uint8_t*>(c.order + c.nseg);
+  launch_image_emit(t->hdr, t->pool, (uint32_t)t->pool_cap, t->p1, t->sbits, base, c.nseg, c.order, c.ld, s);
+  if (int rc = c.lw.alloc(c.nseg)) return rc;
+  HIPCHK(hipMemsetAsync(c.lw.bad, 0, sizeof(uint32_t), s));
+  launch_image_live_scan(t->occ, c.order, (uint32_t)t->max_segs, c.nseg, c.lw.w, s);
+  if (int rc = c.lw.total(c.nseg, s, &c.live)) return rc;
+  if (c.live > (uint64_t)c.nseg * kSlots) return fail(PMDFC_ERR_STATE, "the occupancy words count more than the slots");
+  return PMDFC_OK;
+}
+}  // namespace
+
+uint32_t pmdfc_cceh_packed_scan_block(void) { return kLiveScanBlock; }
+
+int pmdfc_cceh_snapshot_packed(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t* bytes_out, void* stream) {
+  if (!t || !bytes_out) return fail(PMDFC_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipDeviceSynchronize());
+  Canon c;
+  if (int rc = canonical_live(t, s, c)) return rc;
+  const uint32_t nseg = c.nseg;
+  const uint64_t need = packed::total_bytes(nseg, c.live);
+  *bytes_out = need;
+  if (!buf || cap_bytes < need) return fail(PMDFC_ERR_SIZE, "snapshot_packed: the buffer is smaller than the image");
+  if ((uintptr_t)buf & 15u) return fail(PMDFC_ERR_ARG, "snapshot_packed: the buffer must be 16-byte aligned");
+  uint8_t* out = static_cast<uint8_t*>(buf);
+  // the local depths, and the zero padding of the three regions
+  const uint64_t dbytes = image::depth_bytes(nseg);
+  const uint64_t occ_end = packed::occ_offset(nseg) + (uint64_t)nseg * packed::kOccWords * 4;
+  const uint64_t pair_end = packed::pairs_offset(nseg) + c.live * 16;
+  HIPCHK(hipMemsetAsync(out + image::kHeaderBytes, 0, dbytes, s));
+  HIPCHK(hipMemcpyAsync(out + image::kHeaderBytes, c.ld, nseg, hipMemcpyDefault, s));
+  if (packed::pairs_offset(nseg) > occ_end) HIPCHK(hipMemsetAsync(out + occ_end, 0, packed::pairs_offset(nseg) - occ_end, s));
+  if (need > pair_end) HIPCHK(hipMemsetAsync(out + pair_end, 0, need - pair_end, s));
+  PackArgs a{};
+  a.pairs = t->pairs;
+  a.order = c.order;
+  a.max_segs = (uint32_t)t->max_segs;
+  a.cnt = c.lw.w.cnt;
+  a.base = c.lw.w.base;
+  a.occ_out = reinterpret_cast<uint32_t*>(out + packed::occ_offset(nseg));
+  a.pairs_out = reinterpret_cast<ulonglong2*>(out + packed::pairs_offset(nseg));
+  a.bad = c.lw.bad;
+  launch_image_pack(a, nseg, s);
+  HIPCHK(hipGetLastError());
+  uint32_t bad = 0;
+  std::vector<uint8_t> ld(dbytes, 0);
+  HIPCHK(hipMemcpyAsync(&bad, c.lw.bad, sizeof bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(ld.data(), c.ld, nseg, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad) return fail(PMDFC_ERR_STATE, "snapshot_packed: stored keys and occupancy words disagree");
+  image::Header h;
+  h.initial_depth = t->D0;
+  h.shard_bits = t->sbits;
+  h.shard_id = t->shard;
+  h.nseg = nseg;
+  h.live = c.live;
+  h.total_bytes = need;
+  h.min_ld = *std::min_element(ld.begin(), ld.begin() + nseg);
+  h.max_ld = *std::max_element(ld.begin(), ld.begin() + nseg);
+  h.depth = std::max(t->D0, h.max_ld);
+  // (what this call wrote must be what pmdfc_cceh_restore accepts)
+  if (int e = image::validate_depths(h, ld.data())) return fail(PMDFC_ERR_STATE, packed::error_string(e));
+  std::vector<uint8_t> hb(image::kHeaderBytes);
+  packed::encode_header(h, hb.data());
+  HIPCHK(hipMemcpy(out, hb.data(), hb.size(), hipMemcpyDefault));
+  return PMDFC_OK;
+}
+
+int pmdfc_cceh_export_entries(pmdfc_cceh_t* t, uint64_t* d_keys, uint64_t* d_values, uint64_t cap_entries,
+                              uint64_t* n_out, void* stream) {
+  if (!t || !n_out) return fail(PMDFC_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipDeviceSynchronize());
+  Canon c;
+  if (int rc = canonical_live(t, s, c)) return rc;
+  *n_out = c.live;
+  if ((!d_keys && !d_values) || cap_entries < c.live)
+    return fail(PMDFC_ERR_SIZE, "export_entries: the arrays are smaller than the stored entries");
+  PackArgs a{};
+  a.pairs = t->pairs;
+  a.order = c.order;
+  a.max_segs = (uint32_t)t->max_segs;
+  a.cnt = c.lw.w.cnt;
+  a.base = c.lw.w.base;
+  a.keys_out = d_keys;
+  a.vals_out = d_values;
+  a.bad = c.lw.bad;
+  launch_image_pack(a, c.nseg, s);
+  HIPCHK(hipGetLastError());
+  uint32_t bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, c.lw.bad, sizeof bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad) return fail(PMDFC_ERR_STATE, "export_entries: stored keys and occupancy words disagree");
   return PMDFC_OK;
 }
 

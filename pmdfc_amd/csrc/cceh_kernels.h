@@ -157,10 +157,49 @@ struct ScatterArgs {
   uint8_t* ldep;
   uint32_t* pool;
   uint32_t* bad;  // += live keys whose hash prefix is not their segment's, and reserved keys
+  // A packed image (packed_image.h), else occ_img == nullptr: img is then the
+  // `live` dense pairs, occ_img the image's nseg x 32 occupancy words, base[i]
+  // the pairs before segment i (launch_image_live_scan over occ_img).
+  const uint32_t* occ_img;
+  const uint64_t* base;
+  uint64_t live;
 };
 // segment i of the image -> arena id i: pairs, occupancy words, local depth,
 // its directory entries; the live keys are hashed against the segment's prefix
 void launch_image_scatter(const ScatterArgs& a, hipStream_t s);
+// The packed image and the entry export: per-segment live counts from the
+// occupancy words (the pairs are not read) and their exclusive scan in 64 bits,
+// for any nseg: sums per block of kLiveScanBlock counts, a scan of the sums,
+// an add-back.  order != nullptr: occ is the engine's, segment i's words those
+// of arena id de_seg(order[i]); nullptr: occ is an image's occupancy region.
+constexpr uint32_t kLiveScanBlock = 1024;
+inline uint32_t live_scan_blocks(uint32_t nseg) { return (nseg + kLiveScanBlock - 1) / kLiveScanBlock; }
+struct LiveScan {
+  uint64_t* base;  // nseg
+  uint64_t* sums;  // live_scan_blocks(nseg)
+  uint64_t* offs;  // live_scan_blocks(nseg) + 1: the last is the grand total
+  uint32_t* cnt;   // nseg
+};
+void launch_image_live_scan(const uint32_t* occ, const uint32_t* order, uint32_t max_segs, uint32_t nseg,
+                            const LiveScan& w, hipStream_t s);
+// Canonical segment i's stored pairs, in slot order, to rank base[i] on:
+// into a packed image (pairs_out and occ_out, its occupancy region, written
+// from the same ballots), or, pairs_out == nullptr, into the dense arrays
+// keys_out / vals_out (either may be nullptr).  *bad += the segments whose
+// keys do not count what their occupancy words did.
+struct PackArgs {
+  const ulonglong2* pairs;
+  const uint32_t* order;
+  uint32_t max_segs;
+  const uint32_t* cnt;
+  const uint64_t* base;
+  uint32_t* occ_out;
+  ulonglong2* pairs_out;
+  uint64_t* keys_out;
+  uint64_t* vals_out;
+  uint32_t* bad;
+};
+void launch_image_pack(const PackArgs& a, uint32_t nseg, hipStream_t s);
 // flatten the bucketed directory for pure-Get batches: *bits = p1 + max db
 // (the physical depth), flat[x] = the sub-directory entry of index x
 void launch_flatten(const uint64_t* hdr, const uint32_t* pool, uint32_t p1, uint32_t* flat,

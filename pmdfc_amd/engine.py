@@ -87,6 +87,7 @@ EXPORTS = [
     "pmdfc_route_batches",
     "pmdfc_route_mixed_batches",
     "pmdfc_cceh_snapshot", "pmdfc_cceh_restore",
+    "pmdfc_cceh_snapshot_packed", "pmdfc_cceh_export_entries", "pmdfc_cceh_packed_scan_block",
     "pmdfc_cbf_rebuild", "pmdfc_cbf_audit",
 ]
 
@@ -184,6 +185,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_route_mixed_batches": (i32, [P, P, P, P, P, P, P, u64, P, P, P]),
         "pmdfc_cceh_snapshot": (i32, [P, P, u64, C.POINTER(u64), P]),
         "pmdfc_cceh_restore": (i32, [P, P, u64, P]),
+        "pmdfc_cceh_snapshot_packed": (i32, [P, P, u64, C.POINTER(u64), P]),
+        "pmdfc_cceh_export_entries": (i32, [P, P, P, u64, C.POINTER(u64), P]),
+        "pmdfc_cceh_packed_scan_block": (u32, []),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -516,24 +520,43 @@ class CCEH:
                 "keys": keys, "values": vals}
 
     # ---- table image (include/pmdfc_cceh.h; the format: pmdfc_amd/image.py)
-    def snapshot(self) -> torch.Tensor:
+    def snapshot(self, packed: bool = False) -> torch.Tensor:
         """The table's image as a uint8 tensor on the engine's device.  The
         table is unchanged.  Two tables with the same canonical dump give the
-        same bytes."""
+        same bytes.  packed: the packed image, which holds only the stored
+        pairs (about half the bytes at half load); restore() takes either."""
         L = load_library()
+        call = L.pmdfc_cceh_snapshot_packed if packed else L.pmdfc_cceh_snapshot
         n = C.c_uint64()
-        rc = L.pmdfc_cceh_snapshot(self._h, None, 0, C.byref(n), self._d.stream())
+        rc = call(self._h, None, 0, C.byref(n), self._d.stream())
         if rc != PMDFC_ERR_SIZE:  # (the sizing call's only good answer)
             msg = L.pmdfc_last_error()
             raise PmdfcError(f"snapshot sizing failed ({rc}): {msg.decode() if msg else ''}")
         buf = torch.empty(n.value, dtype=torch.uint8, device=self._d.device)
-        _check(L.pmdfc_cceh_snapshot(self._h, buf.data_ptr(), buf.numel(), C.byref(n), self._d.stream()), "snapshot")
+        _check(call(self._h, buf.data_ptr(), buf.numel(), C.byref(n), self._d.stream()), "snapshot")
         return buf[: n.value]
+
+    def items(self):
+        """(keys, values): the stored pairs as two uint64 device tensors
+        (torch.int64 storage, like every key tensor here), in canonical segment
+        order and slot order within a segment.  The table is unchanged."""
+        L = load_library()
+        n = C.c_uint64()
+        rc = L.pmdfc_cceh_export_entries(self._h, None, None, 0, C.byref(n), self._d.stream())
+        if rc != PMDFC_ERR_SIZE:
+            msg = L.pmdfc_last_error()
+            raise PmdfcError(f"items sizing failed ({rc}): {msg.decode() if msg else ''}")
+        keys = torch.empty(n.value, dtype=torch.int64, device=self._d.device)
+        vals = torch.empty(n.value, dtype=torch.int64, device=self._d.device)
+        if n.value:
+            _check(L.pmdfc_cceh_export_entries(self._h, keys.data_ptr(), vals.data_ptr(), n.value, C.byref(n),
+                                               self._d.stream()), "export_entries")
+        return keys, vals
 
     def restore(self, image):
         """Replace the whole table with an image (a uint8 tensor, a numpy
-        array or bytes): one from snapshot(), a file of save(), or
-        pmdfc_amd.image.image_from_dump.  The engine must have the image's
+        array or bytes) of either kind: one from snapshot(), a file of save(),
+        or pmdfc_amd.image.image_from_dump / packed_from_dump.  The engine must have the image's
         initial depth, shard_bits and shard_id; max_batch, max_segments and
         upsert may differ.  Raises PmdfcError for an image the engine refuses
         (the table is then unchanged, or freshly reset if a key lay outside
@@ -548,10 +571,10 @@ class CCEH:
             buf = torch.from_numpy(a.copy() if not a.flags.writeable else a).to(self._d.device)
         _check(load_library().pmdfc_cceh_restore(self._h, buf.data_ptr(), buf.numel(), self._d.stream()), "restore")
 
-    def save(self, path) -> int:
-        """snapshot() to a file of the raw image bytes, through a pinned host
-        buffer.  Returns the byte count."""
-        img = self.snapshot()
+    def save(self, path, packed: bool = False) -> int:
+        """snapshot(packed) to a file of the raw image bytes, through a pinned
+        host buffer.  Returns the byte count."""
+        img = self.snapshot(packed)
         host = torch.empty(img.numel(), dtype=torch.uint8, pin_memory=True)
         host.copy_(img)
         with open(path, "wb") as f:

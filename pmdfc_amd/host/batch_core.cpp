@@ -1070,12 +1070,16 @@ struct MappedBuf {
 };
 }  // namespace
 
-int BatchCore::Save(const char* path) {
+int BatchCore::Save(const char* path) { return save_image(path, false); }
+int BatchCore::SavePacked(const char* path) { return save_image(path, true); }
+
+int BatchCore::save_image(const char* path, bool packed) {
   if (!path) return PMDFC_ERR_ARG;
   int rc = PMDFC_ERR_STATE;
+  const auto snapshot = packed ? pmdfc_cceh_snapshot_packed : pmdfc_cceh_snapshot;
   if (!with_engine([&](hipStream_t st) {
         uint64_t need = 0;
-        rc = pmdfc_cceh_snapshot(t_, nullptr, 0, &need, st);
+        rc = snapshot(t_, nullptr, 0, &need, st);
         if (rc != PMDFC_ERR_SIZE) {
           set_error(std::string("Save: ") + pmdfc_last_error());
           return;
@@ -1086,7 +1090,7 @@ int BatchCore::Save(const char* path) {
           set_error("Save: no pinned host memory for the image");
           return;
         }
-        rc = pmdfc_cceh_snapshot(t_, b.dev, need, &need, st);
+        rc = snapshot(t_, b.dev, need, &need, st);
         if (rc != PMDFC_OK) {
           set_error(std::string("Save: ") + pmdfc_last_error());
           return;

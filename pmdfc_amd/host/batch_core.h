@@ -190,6 +190,7 @@ class BatchCore {
   // PMDFC_OK or the engine's code (PMDFC_ERR_ARG also for a file that cannot
   // be read or written); PMDFC_ERR_STATE from a completion callback.
   int Save(const char* path);
+  int SavePacked(const char* path);  // the packed image (only the stored pairs); Load reads either kind
   int Load(const char* path);
   // chunks after which a serving wave reloaded its LDS copy of the headers
   uint64_t header_reloads() const;
@@ -293,6 +294,7 @@ class BatchCore {
   bool stop_server();    // stop them and wait for them (srv_mu_ held)
   template <class F>
   bool with_engine(F f);  // flush, stop the waves, f(stream), start them again
+  int save_image(const char* path, bool packed);  // Save / SavePacked
   int rebuild_bf(void* stream, uint64_t* stored);  // (inside with_engine) rebuild + pack + one sync
 
   pmdfc_cceh_t* t_ = nullptr;

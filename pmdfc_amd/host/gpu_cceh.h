@@ -99,6 +99,7 @@ class GpuCCEH : public IHash {
   // image, which a device table never needs.  Load rebuilds and packs an
   // attached counting BF from the loaded table (the filter is not in the file).
   bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
+  bool SavePacked(const char* path) { return core_.SavePacked(path) == PMDFC_OK; }  // only the stored pairs
   bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
 
   // ---- whole-batch entry points (host arrays, through the queue in order)

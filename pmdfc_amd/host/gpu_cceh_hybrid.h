@@ -83,6 +83,7 @@ class GpuCCEHHybrid : public ICCEH {
   // image, which a device table never needs.  Load rebuilds and packs an
   // attached counting BF from the loaded table (the filter is not in the file).
   bool Save(const char* path) { return core_.Save(path) == PMDFC_OK; }
+  bool SavePacked(const char* path) { return core_.SavePacked(path) == PMDFC_OK; }  // only the stored pairs
   bool Load(const char* path) { return core_.Load(path) == PMDFC_OK; }
   // NUMA_KV keeps no filter of its own; a server that ships one per index
   // attaches it here: every per-op Insert counts in it, extent heads do not

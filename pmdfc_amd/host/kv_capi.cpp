@@ -156,6 +156,11 @@ int pmdfc_kv_save(pmdfc_kv_t* kv, const char* path) {
   return kv->core->Save(path);
 }
 
+int pmdfc_kv_save_packed(pmdfc_kv_t* kv, const char* path) {
+  if (!kv || !path) return PMDFC_ERR_ARG;
+  return kv->core->SavePacked(path);
+}
+
 int pmdfc_kv_load(pmdfc_kv_t* kv, const char* path) {
   if (!kv || !path) return PMDFC_ERR_ARG;
   return kv->core->Load(path);

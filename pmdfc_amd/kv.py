@@ -30,7 +30,7 @@ KV_EXPORTS = [
     "pmdfc_kv_create", "pmdfc_kv_destroy", "pmdfc_kv_insert", "pmdfc_kv_get", "pmdfc_kv_ops",
     "pmdfc_kv_ops_async", "pmdfc_kv_flush", "pmdfc_kv_utilization", "pmdfc_kv_capacity",
     "pmdfc_kv_find_anyway", "pmdfc_kv_stats", "pmdfc_kv_dump", "pmdfc_kv_phase", "pmdfc_kv_last_error",
-    "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_load",
+    "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_save_packed", "pmdfc_kv_load",
     "pmdfc_kv_attach_cbf", "pmdfc_kv_rebuild_cbf", "pmdfc_kv_audit_cbf",
 ]
 
@@ -69,6 +69,7 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_create_error": (C.c_char_p, []),
         "pmdfc_kv_phase": (i32, [P, P]),
         "pmdfc_kv_save": (i32, [P, C.c_char_p]),
+        "pmdfc_kv_save_packed": (i32, [P, C.c_char_p]),
         "pmdfc_kv_load": (i32, [P, C.c_char_p]),
         "pmdfc_kv_attach_cbf": (i32, [P, P]),
         "pmdfc_kv_rebuild_cbf": (i32, [P, C.POINTER(u64)]),
@@ -205,9 +206,12 @@ class KV:
             self._err("stats", rc)
         return {n: getattr(s, n) for n, _ in Stats._fields_}
 
-    def save(self, path):
-        """The table's image (CCEH.snapshot) to a file, after every queued op."""
-        rc = load_kv_library().pmdfc_kv_save(self._h, os.fsencode(path))
+    def save(self, path, packed: bool = False):
+        """The table's image (CCEH.snapshot) to a file, after every queued op;
+        packed: the packed image (only the stored pairs), which load() reads
+        just the same."""
+        L = load_kv_library()
+        rc = (L.pmdfc_kv_save_packed if packed else L.pmdfc_kv_save)(self._h, os.fsencode(path))
         if rc != 0:
             self._err("save", rc)
 
