@@ -58,7 +58,22 @@ extern "C" {
 #define PMDFC_ST_RESERVED_KEY 3  /* key == INVALID (2^64-1) or SENTINEL (2^64-2) */
 #define PMDFC_ST_UNSPLITTABLE 4  /* window holds 32 entries of this key's hash */
 #define PMDFC_ST_DEPTH_LIMIT 5   /* a split would exceed global depth 30 */
-#define PMDFC_ST_CAPACITY 6      /* segment arena exhausted */
+#define PMDFC_ST_CAPACITY 6      /* segment arena or sub-directory pool exhausted (see below) */
+/* PMDFC_ST_CAPACITY, the contract.  Only an Insert whose 32-slot window is full
+ * can get it: the split that would make room was denied, because max_segments
+ * segment ids are handed out or the sub-directory pool cannot take the growth
+ * the split needs (then pmdfc_cceh_stats_t.error_flags bit 1 is set as well).
+ * The op stores nothing; an Insert whose window has a free slot still succeeds,
+ * in the same batch and in every later one, a stored key still answers HIT,
+ * and a key whose 32 copies fill its window still answers UNSPLITTABLE.  The
+ * table stays valid: every image, export and filter rebuild of it is that of
+ * the table the directory shows.  From the first denial on the table may stop
+ * splitting even where a few ids are left (a directory bucket is granted all
+ * its splits of a round or none), and it stays so until pmdfc_cceh_reset or
+ * pmdfc_cceh_restore, after which it splits again.  pmdfc_cceh_stats_t.segments
+ * is the number of segments in the directory, never more than max_segments:
+ * ids counted past the arena's end, and ids retired empty because the pool
+ * denied their split after they were taken, are not in it. */
 #define PMDFC_ST_FILTERED 7      /* bloom-negative: miss without an index probe */
 #define PMDFC_ST_WRONG_SHARD 8   /* key's hash prefix is owned by another shard */
 #define PMDFC_ST_ROUTE_OVERFLOW 9 /* routed batch: the owner's carry was full (carry_cap ops waiting), op not applied */

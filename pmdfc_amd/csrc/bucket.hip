@@ -1082,6 +1082,7 @@ struct RunCtx {  // what one run needs (passed by value: no kernarg copies)
   const uint16_t* upos;  // upsert, first apply pass: pre-batch key slots by op index, else null
   ulonglong2* wl_kv;  // this bucket's wait list (k_apply parks the rest of a blocked run there)
   uint32_t* wl_op;
+  uint32_t pfix, pool_cap;  // final pass: where the sub-directory grows, and the pool's end
 };
 
 // Upsert (last-writer-wins, CCEH_hybrid.cpp:153's overwrite clause enabled):
@@ -1324,6 +1325,16 @@ __device__ __forceinline__ uint2 apply_run(RunCtx a, BucketLds<FINAL, !FINAL && 
       }
       waited += q1 - q;
       break;
+    }
+    // the final pass grows the sub-directory itself: a split whose growth the
+    // pool can no longer take (pool_cur only grows) fails before it takes a
+    // child id
+    if (const uint32_t nb = L + 1 - lbase; nb > a.db && !(a.pfix && nb <= kFixedBits) &&
+        (uint64_t)ld_u32_l2(&a.ctl->pool_cur) + (1ULL << nb) > a.pool_cap) {
+      atomicOr(&a.ctl->err, 1u);
+      a.st[op] = 6;  // PMDFC_ST_CAPACITY
+      S.pend[i] = 0;
+      continue;
     }
     const uint32_t si = atomicAdd(&S.nsplit, 1u);
     if (si >= kSplitCap) {
@@ -2519,6 +2530,16 @@ __device__ __forceinline__ void grow_and_split(const BucketArgs& a, uint32_t w, 
         a.st[S.op[i] & kOpMask] = 6;
         S.pend[i] = 0;
       }
+      // their child ids are taken: retired empty, so that the arena walks
+      // by id find no stale entries under them
+      uint32_t nd = 0;
+      for (uint32_t s = 0; s < ns; ++s) {
+        const uint64_t e = S.split[s];
+        if (e == ~0ULL) continue;
+        retire_segment(a.pairs, a.occ, a.ldep, (uint32_t)(e >> 21));
+        ++nd;
+      }
+      if (lane == 0 && nd) atomicAdd(&a.ctl->dead, nd);
       __builtin_amdgcn_wave_barrier();
       return;
     }
@@ -2683,7 +2704,8 @@ __device__ __forceinline__ uint32_t bucket_body(const BucketArgs& a, const uint3
       const RunCtx rc{a.pairs, a.occ, a.vout, a.st, a.ctl, a.req + (size_t)w * kSplitCap,
                       a.reqop + (size_t)w * kSplitCap, a.mixed, a.max_segments, full, (uint32_t)(!FINAL && a.mode == 2),
                       (!FINAL && FIRST) ? srow : nullptr,
-                      a.sbits, a.p1, db, a.upsert, (FIRST && a.upsert) ? a.upos : nullptr, wl_kv, wl_op};
+                      a.sbits, a.p1, db, a.upsert, (FIRST && a.upsert) ? a.upos : nullptr, wl_kv, wl_op, a.pfix,
+                      (uint32_t)a.pool_cap};
       apply_runs<FINAL, MIXED>(rc, S, nruns, !FINAL && ldir.on && !wide, c);
       if (!FINAL && FIRST) stamp(srow0, kBsRunsDone, lane == 0);
       // ---- write the claims
@@ -3303,7 +3325,15 @@ __global__ __launch_bounds__(64 * kSplitWaves, 2) void k_split(SplitArgs a) {
       a.act[cex + (el.y >> 20)] = w;
       if (!ok) a.ctl->full = 1;
     }
-    if (!ok) continue;  // (uniform over a team: one k)
+    if (!ok) {  // (uniform over a team: one k)
+      // denied for the pool with its ids inside the granted prefix (handout
+      // counts them): each request's child id is retired empty
+      if (gs + nr <= a.max_segments && (!team || wv == 0)) {
+        retire_segment(a.pairs, a.occ, a.ldep, seg0 + k);
+        if (lane == 0) atomicAdd(&a.ctl->dead, 1u);
+      }
+      continue;
+    }
     bool b = false;
     uint64_t* stp = a.stamps && k < kSplitStamps ? a.stamps + (size_t)k * 8 : nullptr;
     stamp(stp, kSsStart, lane == 0 && (!team || wv == 0));

@@ -205,7 +205,8 @@ __global__ __launch_bounds__(256) void k_cbf_pack(const uint8_t* __restrict__ cn
 
 // The scan over the stored keys (pmdfc_cbf_rebuild / pmdfc_cbf_audit): arena
 // segments [0, min(ctl->nsegs, max_segs)) -- every id below nsegs is live
-// (child 0 of a split keeps its parent's id), ids from nsegs on may hold
+// (child 0 of a split keeps its parent's id) or retired empty (ctl->dead:
+// its split was denied after the id was taken), ids from nsegs on may hold
 // anything and are never read -- a workgroup of four waves per segment and
 // step of the grid-stride loop, 16 B per lane, the four loads of a segment
 // issued together (k_image_gather's shape) and one segment ahead of the

@@ -377,7 +377,7 @@ __device__ __forceinline__ void cbf_increment(uint8_t* cnt, uint64_t m, uint32_t
 // Device-side control block (one per engine).  Nothing on the insert path
 // reads it back: the host copies it only for stats/dump.
 struct DevCtl {
-  uint32_t nsegs;        // segment ids handed out (may overshoot max on CAPACITY)
+  uint32_t nsegs;        // segment ids handed out (may overshoot max on CAPACITY; see dead)
   uint32_t pool_cur;     // sub-directory pool entries handed out (may overshoot the pool likewise)
   uint32_t max_ld;       // max local depth (global bits)
   uint32_t err;          // sticky: 1 pool exhausted, 2 round guard tripped
@@ -401,7 +401,24 @@ struct DevCtl {
   uint32_t ins_total;    // mixed batch in insert-set mode: its inserts (k_mixed_get_iset sums k_mixed_prep's per-block
                          // counts; k_mixed_verify's choice of how to empty the set); the join mode never sets it
   uint32_t njoin;        // k_mixed_get -> k_mixed_join: tag of the last mixed batch with a joining Get
+  uint32_t dead;         // ids below nsegs whose split was denied after the id was taken (the pool ran out):
+                         // retired empty (retire_segment), in no directory; live segments = min(nsegs, max) - dead
 };
+
+// A segment id that was handed out for a split the pool then denied: the
+// segment is never entered in a directory, but everything that walks the
+// arena by id (min(ctl->nsegs, max_segments): the filter rebuild, Utilization,
+// k_min_ldep) reads it, so it is left empty, at the deepest local depth (it
+// never lowers the smallest one).  One whole wave; the caller counts it in
+// ctl->dead.  id < max_segments.
+__device__ __forceinline__ void retire_segment(ulonglong2* __restrict__ pairs, uint32_t* __restrict__ occ,
+                                               uint8_t* __restrict__ ldep, uint32_t id) {
+  const uint32_t lane = __lane_id() & 63u;
+  ulonglong2* p = pairs + (size_t)id * kSlots;
+  for (uint32_t j = lane; j < kSlots; j += 64u) p[j] = make_ulonglong2(kInvalid, 0ULL);
+  if (lane < 32u) occ[(size_t)id * 32u + lane] = 0u;
+  if (lane == 0) ldep[id] = (uint8_t)kMaxDepth;
+}
 
 // Drop log of a mixed batch (kDropLog x {key, op index of the insert whose
 // split dropped it}): a split's Insert4split drops (CCEH_hybrid.cpp:24-27)

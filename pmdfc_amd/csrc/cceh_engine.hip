@@ -1517,7 +1517,9 @@ int pmdfc_cceh_stats(pmdfc_cceh_t* t, pmdfc_cceh_stats_t* out) {
   HIPCHK(hipMemcpy(hd.data(), t->hdr, hd.size() * 8, hipMemcpyDeviceToHost));
   uint32_t maxdb = 0;
   for (auto v : hd) maxdb = std::max(maxdb, hdr_db(v));
-  const uint64_t nsegs = std::min<uint64_t>(c.nsegs, t->max_segs);
+  // the segments in the directory: ids handed out, less the overshoot of a
+  // full arena and the ids retired empty when the pool denied their split
+  const uint64_t nsegs = std::min<uint64_t>(c.nsegs, t->max_segs) - c.dead;
   out->depth = std::max(t->D0, max_ld);
   out->phys_depth = t->sbits + t->p1 + maxdb;
   out->segments = nsegs;
@@ -1551,12 +1553,12 @@ int pmdfc_cceh_utilization(pmdfc_cceh_t* t, double* out) {
   HIPCHK(hipDeviceSynchronize());
   int rc = read_ctl(t, (hipStream_t)0);
   if (rc) return rc;
-  const uint64_t nsegs = std::min<uint64_t>(t->hctl->nsegs, t->max_segs);
+  const uint64_t nsegs = std::min<uint64_t>(t->hctl->nsegs, t->max_segs);  // (retired ids are empty)
   HIPCHK(hipMemset(t->popc, 0, sizeof(unsigned long long)));
   launch_popcount(t->occ, nsegs * 32, t->popc, (hipStream_t)0);
   unsigned long long c = 0;
   HIPCHK(hipMemcpy(&c, t->popc, sizeof c, hipMemcpyDeviceToHost));
-  *out = (double)c / ((double)nsegs * kSlots) * 100.0;
+  *out = (double)c / ((double)(nsegs - t->hctl->dead) * kSlots) * 100.0;
   return PMDFC_OK;
 }
 

@@ -667,3 +667,184 @@ def extent_expand(conv, keys, clusters, lens, vals, heads_fn):
         hk.extend(h)
         hv.extend([v] * len(h))
     return np.array(hk, np.uint64), np.array(hv, np.uint64)
+
+
+# hash64 (oracle.hash64, csrc/cceh_device.h) is a bijection on 64-bit values:
+# multiplications by the odd constant 0xc6a4a7935bd1e995, x ^= x >> 47 steps
+# (their own inverse: 2 * 47 > 64) and an xor with a constant.  Its inverse
+# makes a key of any chosen hash, so a test can place keys by segment prefix,
+# by child bit at every depth and by home line without a search.
+_HASH_MUL = np.uint64(0xc6a4a7935bd1e995)
+_HASH_MUL_INV = np.uint64(0x5f7a0ea7e59b19bd)  # _HASH_MUL * _HASH_MUL_INV == 1 mod 2^64
+_HASH_SEED = np.uint64(0xc70697 ^ ((8 * 0xc6a4a7935bd1e995) & (2**64 - 1)))
+
+
+def unhash64(h) -> np.ndarray:
+    """The keys whose hash64 is h (a uint64 array): hash64 run backwards."""
+    s47 = np.uint64(47)
+    with np.errstate(over="ignore"):
+        x = np.ascontiguousarray(h, dtype=np.uint64).copy()
+        x ^= x >> s47
+        x *= _HASH_MUL_INV
+        x ^= x >> s47
+        x *= _HASH_MUL_INV
+        x ^= _HASH_SEED
+        x *= _HASH_MUL_INV
+        x ^= x >> s47
+        x *= _HASH_MUL_INV
+    return x
+
+
+def keys_from_hash_fields(prefix, pbits, line, count, first=0, below=None):
+    """`count` distinct keys by hash field: the top `pbits` hash bits are
+    `prefix`, the home line h & 0xFF is `line`, and the bits in between number
+    the keys first, first + 1, ... (distinct hashes, so distinct keys).
+    below = (bit position b, width): the numbers go into the `width` bits
+    that end at hash bit b (b = 63 is the top bit), so keys that share their
+    top bits down to b + 1 differ right below them; default: the low end of
+    the middle field, bits 8 and up."""
+    n = np.arange(first, first + count, dtype=np.uint64)
+    if below is None:
+        shift, width = 8, 56 - pbits
+    else:
+        b, width = below
+        shift = b - width + 1
+        assert shift >= 8 and b < 64 - pbits
+    assert first + count <= 1 << width
+    h = (np.uint64(prefix) << np.uint64(64 - pbits)) if pbits else np.uint64(0)
+    h = h | (n << np.uint64(shift)) | np.uint64(line)
+    return unhash64(h)
+
+
+# Streams that run a table out of room (tests/test_gpu_limits.py; the model of
+# the exhausted table is tests/limits_ref.py).  Every stream is chosen so that
+# no split of the serial table drops an entry (split_loss == 0 on an oracle
+# with no segment limit: tests/test_limits_ref.py asserts it for each case),
+# which lets a test account for every stored pair.
+def limit_stream(seed, max_segments, load=3.0):
+    """Uniform keys, `load` times the slots of max_segments segments."""
+    keys = uniform_keys(seed, 0, int(load * max_segments * 1024))
+    return keys, _vals(keys, 0x11A7)
+
+
+def limit_upsert_stream(seed, max_segments, load=3.0, p_re=0.2):
+    """limit_stream where ~20% of the inserts repeat an earlier key with a new
+    value (under upsert: UPDATED where the key is stored, whatever the table's
+    state; a repeat of a key that failed fails or succeeds on its own)."""
+    keys, _ = limit_stream(seed, max_segments, load)
+    n = keys.size
+    rng = np.random.default_rng(seed)
+    rep = rng.random(n) < p_re
+    rep[0] = False
+    src = (rng.random(n) * np.arange(n)).astype(np.int64)
+    keys = keys.copy()
+    base = keys.copy()
+    keys[rep] = base[src[rep]]
+    return keys, np.arange(1, n + 1, dtype=np.uint64)
+
+
+def limit_mixed_batches(seed, keys, vals, n_ins, n_get):
+    """The insert stream cut into mixed batches of n_ins inserts and n_get
+    Gets, shuffled together: Gets of keys of earlier batches (stored, or
+    failed and so absent), of keys this batch inserts (before or after their
+    insert, which succeeds or fails) and of keys no batch inserts."""
+    rng = np.random.default_rng(seed)
+    never = uniform_keys(seed + 1000, 0, 4096)
+    out = []
+    for a in range(0, keys.size, n_ins):
+        ik, iv = keys[a:a + n_ins], vals[a:a + n_ins]
+        g = [rng.choice(ik, n_get // 3), rng.choice(never, n_get // 6)]
+        g.append(rng.choice(keys[:a] if a else never, n_get - g[0].size - g[1].size))
+        g = np.concatenate(g)
+        k = np.concatenate([ik, g])
+        v = np.concatenate([iv, np.zeros(g.size, np.uint64)])
+        o = np.concatenate([np.full(ik.size, OP_INSERT, np.uint8), np.full(g.size, OP_GET, np.uint8)])
+        p = rng.permutation(k.size)
+        out.append((o[p], k[p], v[p]))
+    return out
+
+
+DEEP_CHAIN_DEPTH = 9     # the deep-chain tables start with 2^9 segments
+DEEP_CHAIN_LINES = (7, 255, 130, 252, 64)  # home lines of the groups (255, 252: the window wraps)
+
+
+def deep_chain_stream(D, seed, groups=3, n_uniform=12000, depth=DEEP_CHAIN_DEPTH):
+    """A few segments with a long common hash prefix.  Group g is 33 keys of
+    one home line whose hashes share their top D - 1 bits and differ right
+    below them (the 6 bits from hash bit 64 - D down number the keys, so bit
+    64 - D is 0 for the first 32 keys and 1 for the last).  32 of them fill
+    the window; the 33rd splits its segment, and every split down to local
+    depth D - 1 leaves all 32 in one child with the window still full: a chain
+    of D - depth splits (depth: the table's initial depth) that ends at local
+    depth D, with as many new segments, and a directory of depth D.  The
+    groups lie in different initial segments.  Returns (keys, values, the groups' keys): a shuffle of
+    n_uniform uniform keys and the groups, each group in its own order."""
+    rng = np.random.default_rng(seed)
+    tops = rng.choice(1 << depth, groups, replace=False)
+    gk = []
+    for g in range(groups):
+        rest = int(rng.integers(0, 1 << (D - 1 - depth)))
+        prefix = (int(tops[g]) << (D - 1 - depth)) | rest
+        gk.append(keys_from_hash_fields(prefix, D - 1, DEEP_CHAIN_LINES[g % len(DEEP_CHAIN_LINES)], 33,
+                                        below=(64 - D, 6)))
+    uni = uniform_keys(seed, 0, n_uniform)
+    # positions: the uniform keys keep their order, each group keeps its own
+    tag = np.concatenate([np.full(uni.size, -1)] + [np.full(33, g) for g in range(groups)])
+    tag = tag[rng.permutation(tag.size)]
+    keys = np.empty(tag.size, np.uint64)
+    keys[tag == -1] = uni
+    for g in range(groups):
+        keys[tag == g] = gk[g]
+    return keys, _vals(keys, 0xD33B), gk
+
+
+# The exhaustion cases of tests/test_gpu_limits.py: name -> the table (initial
+# depth, max_segments = 2^depth + extra), the stream's seed, the batch size,
+# the engine's max_batch (it sets the full bucket resolution p1max =
+# floor(log2(max_batch)) - 7, which decides the path a batch takes) and what
+# else the case sets.  Seeds: every (seed, depth, extra) below gives
+# split_loss == 0 on an oracle with no segment limit (asserted by
+# test_limits_ref.py::test_limit_streams_drop_nothing); a seed that did not
+# was replaced by the next integer (none had to be).
+LIMIT_CASES = {
+    # one launch (k_mixed_small): batches up to 256 ops
+    "small23": dict(depth=2, extra=1, seed=11, batch=23, max_batch=4096),
+    "small64": dict(depth=2, extra=2, seed=12, batch=64, max_batch=4096),
+    "small256": dict(depth=2, extra=7, seed=13, batch=256, max_batch=4096),
+    # two launches (k_part + k_medium) at full bucket resolution: p1max = 2 and 6
+    "medium1000": dict(depth=2, extra=7, seed=13, batch=1000, max_batch=1000),
+    "medium8192": dict(depth=6, extra=1, seed=14, batch=8192, max_batch=8192),
+    # the general path, lean first pass: all 64 buckets request splits in the
+    # round that exhausts the arena; and on a table below its bucket resolution
+    "general65536": dict(depth=6, extra=7, seed=15, batch=65536, max_batch=65536),
+    "general2000_ramp": dict(depth=2, extra=2, seed=12, batch=2000, max_batch=16384),
+    "fast_apply0": dict(depth=6, extra=2, seed=16, batch=65536, max_batch=65536, env={"PMDFC_FAST_APPLY": "0"}),
+    "cp0": dict(depth=6, extra=7, seed=15, batch=16384, max_batch=16384, env={"PMDFC_CP": "0"}),
+    "team0": dict(depth=6, extra=1, seed=14, batch=65536, max_batch=65536, env={"PMDFC_SPLIT_TEAM_MAX": "0"}),
+    # mixed batches (batch inserts + gets Gets), small, medium and general with each forced mode
+    "mixed_small": dict(depth=2, extra=1, seed=11, batch=150, gets=100, max_batch=4096),
+    "mixed_medium": dict(depth=2, extra=7, seed=13, batch=600, gets=400, max_batch=1000),
+    "mixed_join0": dict(depth=6, extra=7, seed=15, batch=12000, gets=8000, max_batch=65536,
+                        env={"PMDFC_MIXED_JOIN": "0"}),
+    "mixed_join1": dict(depth=6, extra=7, seed=15, batch=12000, gets=8000, max_batch=65536,
+                        env={"PMDFC_MIXED_JOIN": "1"}),
+    "upsert_small": dict(depth=2, extra=2, seed=17, batch=256, max_batch=4096, upsert=True),
+    "upsert_general": dict(depth=6, extra=2, seed=18, batch=65536, max_batch=65536, upsert=True),
+    "upsert_mixed": dict(depth=6, extra=2, seed=18, batch=12000, gets=8000, max_batch=65536, upsert=True),
+}
+# pipelined Insert_batches and the served front-end: (depth, extra, seed) of LIMIT_CASES rows
+LIMIT_PIPELINED = dict(depth=6, extra=7, seed=15, batch=12000, max_batch=16383)
+LIMIT_SERVED = dict(depth=2, extra=2, seed=12, batch=1500, max_batch=8192)
+
+# deep chains inside the pool: (D, seed), each seed with split_loss == 0 as above
+DEEP_CHAIN_CASES = [(12, 21), (18, 22), (22, 23)]
+# past the pool: tables whose pool is a few thousand entries beyond the fixed
+# slots, through the small, the medium and the general path (batch: ops per
+# batch; tail: uniform keys before each later retry of the chains' triggers)
+_DEEP_POOL_D5 = dict(D=22, seed=24, groups=3, depth=5, n_uniform=4000, max_batch=4096, max_segments=128, tail=500)
+DEEP_POOL_CASES = {
+    "small": dict(_DEEP_POOL_D5, batch=200),
+    "medium": dict(_DEEP_POOL_D5, batch=512),
+    "general": dict(D=22, seed=25, groups=3, depth=7, n_uniform=12000, max_batch=16384, max_segments=256, tail=8200,
+                    batch=12200),
+}
