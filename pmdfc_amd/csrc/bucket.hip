@@ -1599,8 +1599,8 @@ __device__ __forceinline__ uint32_t fc_full(const BucketArgs& a, uint32_t full, 
 // (one bin per segment); the caller defines it.
 // UPS (last-writer-wins, the lean pass): upd[j] is the pre-batch slot of
 // insert j's key in its window (0xFFFF: absent; the caller probed it, with
-// no duplicate key in the bucket) and occw[2j], occw[2j+1] its two occupancy
-// words (loaded by the caller for that probe).  An insert whose key is
+// no duplicate key in the bucket) and owin[j] its window's occupancy bits
+// (loaded by the caller for that probe).  An insert whose key is
 // stored claims nothing: it overwrites its slot (PMDFC_ST_UPDATED) unless its
 // segment splits before it in the batch, then it is parked like the others.
 // A lane's kPer ops as fast_claim reads them: key, value, rop word, whether
@@ -1753,7 +1753,7 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
                                            const uint64_t* s_key, ulonglong2* wl_kv, uint32_t* wl_op,
                                            uint32_t* s_nsplit, uint32_t* s_nreq, uint32_t* s_need,
                                            const LaneOps& o, BinF bin, WaveStat& c, uint64_t* srow,
-                                           const uint32_t* upd = nullptr, const uint32_t* occw = nullptr) {
+                                           const uint32_t* upd = nullptr, const uint32_t* owin = nullptr) {
   const uint32_t lane = __lane_id() & 63u;
   const uint32_t full = a.ctl->full;
   const FcScr<NL, NB> F(sc);
@@ -1762,21 +1762,18 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
   bool pc[kPer];
 #pragma unroll
   for (int j = 0; j < kPer; ++j) pc[j] = o.pq[j] && (!UPS || upd[j] == 0xFFFFu);
-  // each insert's two occupancy words (its window), in flight during the LDS work
-  uint32_t olo[kPer], ohi[kPer];
+  // each insert's occupancy window (UPS: upsert_probe loaded it), in flight during the LDS work
+  WinLd ow[UPS ? 1 : kPer];
+  if constexpr (!UPS) {
 #pragma unroll
-  for (int j = 0; j < kPer; ++j) {
-    if (!pc[j]) continue;
-    if constexpr (UPS) {
-      olo[j] = occw[2 * j];
-      ohi[j] = occw[2 * j + 1];
-    } else {
-      const uint32_t* og = a.occ + (size_t)de_seg(o.e8[j]) * 32u;
-      const uint32_t wi = o.home8[j] >> 3;
-      olo[j] = ld_u32_l2(og + wi);
-      ohi[j] = ld_u32_l2(og + ((wi + 1u) & 31u));
-    }
+    for (int j = 0; j < kPer; ++j)
+      if (pc[j]) ow[j] = ld_window_l2(a.occ + (size_t)de_seg(o.e8[j]) * 32u, o.home8[j] >> 3);
   }
+  // bit t: slot home * 4 + t taken before the pass
+  const auto wbits = [&](int j) -> uint32_t {
+    if constexpr (UPS) return owin[j];
+    else return window_bits(ow[j], o.home8[j]);
+  };
 #pragma unroll
   for (int t = 0; t < (int)(2 * NB * 8 / 64); ++t) hm[t * 64 + lane] = 0;  // hm and dm
   if (lane < NB) {
@@ -1805,7 +1802,7 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
     if (!pc[j]) continue;
     const uint32_t h = o.home8[j], xc = bin(j), base = xc * 8u, l0 = (h - 7u) & 255u;
     const uint32_t wo = h * 4u;
-    const uint32_t win = __builtin_amdgcn_alignbit(ohi[j], olo[j], wo & 31u);  // bit t: slot wo + t taken
+    const uint32_t win = wbits(j);  // bit t: slot wo + t taken
     // lines another insert's window may claim in: its home within 7 lines
     // before this one's, up to the line of this one's claim (the whole window
     // when it is full) -- outside that, neither claim can see the other
@@ -1849,7 +1846,7 @@ __device__ __forceinline__ bool fast_claim(const BucketArgs& a, uint32_t w, uint
     const uint32_t xc = bin(j), p = dst[xc] + ((st[j] >> 16) & 0xFFu);
     st[j] = kDep | (p << 16);
     F.opk[p] = ((o.rop[j] & kOpMask) << 8) | o.home8[j];
-    F.snap[p] = __builtin_amdgcn_alignbit(ohi[j], olo[j], (o.home8[j] * 4u) & 31u);  // the window before the pass
+    F.snap[p] = wbits(j);  // the window before the pass
     F.res[p] = 0;
     F.slot8[p] = (uint8_t)((uint32_t)j * 64u + lane);
     F.binp[p] = (uint8_t)xc;
@@ -1966,9 +1963,16 @@ __device__ __forceinline__ uint32_t compact_prefetched(const BucketArgs& a, cons
 // Lane xs (< kPartSubs): the record count of the partition bucket's
 // sub-region xs.  The load is issued with the prefetch; sub_count_max, the
 // largest of them on every lane, waits for it.
-__device__ __forceinline__ uint32_t sub_count_load(const BucketArgs& a, uint32_t pb) {
+// (sub_count_issue: the load alone, the count not yet clamped to the
+// sub-region.  Every lane loads and keeps a count, lane l that of sub-region
+// l % kPartSubs: a load under a branch is waited for inside it, ahead of the
+// loads issued after it)
+__device__ __forceinline__ uint32_t sub_count_issue(const BucketArgs& a, uint32_t pb) {
   const uint32_t lane = __lane_id() & 63u;
-  return lane < kPartSubs ? min(a.cursor[(lane << (a.p1 - a.sbb)) + pb], a.capx) : 0u;
+  return a.cursor[((lane % kPartSubs) << (a.p1 - a.sbb)) + pb];
+}
+__device__ __forceinline__ uint32_t sub_count_load(const BucketArgs& a, uint32_t pb) {
+  return min(sub_count_issue(a, pb), a.capx);
 }
 __device__ __forceinline__ uint32_t sub_count_max(uint32_t csub) {
   uint32_t cmax = csub;
@@ -3025,9 +3029,10 @@ __device__ __forceinline__ bool tiny_batch(const BucketArgs& a, BucketLds<true, 
       a.vout[lane] = v;
       a.st[lane] = st;
     } else {
-      const uint32_t wi0 = (uint32_t)(h & 0xFF) * 4u, wi = wi0 >> 5, wn = (wi + 1u) & 31u;
+      const uint32_t wi0 = (uint32_t)(h & 0xFF) * 4u, wi = wi0 >> 5;
       uint32_t* og = a.occ + (size_t)seg * 32u;
-      const uint32_t lo = ld_u32_l2(og + wi), hi = ld_u32_l2(og + wn);
+      const uint2 ow = window_words(ld_window_l2(og, wi), wi);
+      const uint32_t lo = ow.x, hi = ow.y;
       const int pos = window_first_free(lo, hi, wi0);
       if (pos < 0) {
         general = true;  // full window: the ordered path splits
@@ -3448,6 +3453,14 @@ struct FastLds {
 // overlays the waves' claim scratch (4 workgroups per CU: 8 waves per SIMD).
 constexpr uint32_t kCpWaves = 1u << kCpSbb;
 constexpr uint32_t kCpPre = 192;  // records staged per sub-region (mean 128 at 1M ops / 1,024 buckets / 8 sub-regions)
+// Staged in two stages: records [0, kCpPre1) of every sub-region before
+// anything is known, [kCpPre1, kCpPre) once the sub-region counts have
+// arrived and only where the record is live -- at the mean of 128 the second
+// stage loads ~4 records per sub-region instead of 64 stale ones.
+#ifndef PMDFC_CP_LEAN_STAGE
+#define PMDFC_CP_LEAN_STAGE 1  // (A/B builds) 0: all kCpPre records unconditionally
+#endif
+constexpr uint32_t kCpPre1 = PMDFC_CP_LEAN_STAGE ? 128 : kCpPre;
 struct CpLds {
   union {
     FastLds<false> w[kCpWaves];
@@ -3488,12 +3501,12 @@ __device__ __forceinline__ bool dense_bins(uint32_t* seen, const bool (&pq)[kPer
 // The lean pass in last-writer-wins mode: each insert's window is probed for
 // its key over the occupied prefix (a stored key lies before the window's
 // first free slot: nothing is deleted).  upd[j]: the slot of insert j's key
-// (0xFFFF: absent); occw[2j], occw[2j + 1]: its window's occupancy words, for
+// (0xFFFF: absent); owin[j]: its window's occupancy bits (window_bits), for
 // fast_claim.  False: two inserts of one key, nothing probed (the general
 // pass takes the bucket).
 __device__ __forceinline__ bool upsert_probe(const BucketArgs& a, const bool (&pq)[kPer], const uint64_t (&rk)[kPer],
                                              const uint32_t (&e8)[kPer], const uint32_t (&home8)[kPer],
-                                             uint32_t (&upd)[kPer], uint32_t (&occw)[2 * kPer]) {
+                                             uint32_t (&upd)[kPer], uint32_t (&owin)[kPer]) {
   const uint32_t lane = __lane_id() & 63u;
   // two inserts of one key: the general pass (equal keys have equal hashes;
   // a 32-bit hash collision only sends the bucket there too)
@@ -3510,19 +3523,16 @@ __device__ __forceinline__ bool upsert_probe(const BucketArgs& a, const bool (&p
   // the window's occupancy words, then its occupied prefix, line by line
   // (the loads of all of a lane's inserts in flight together)
   uint32_t nl[kPer];
+  WinLd ow[kPer];
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
     upd[j] = 0xFFFFu;
-    occw[2 * j] = occw[2 * j + 1] = 0;
-    if (!pq[j]) continue;
-    const uint32_t* og = a.occ + (size_t)de_seg(e8[j]) * 32u;
-    const uint32_t wi = home8[j] >> 3;
-    occw[2 * j] = ld_u32_l2(og + wi);
-    occw[2 * j + 1] = ld_u32_l2(og + ((wi + 1u) & 31u));
+    ow[j] = WinLd{};
+    if (pq[j]) ow[j] = ld_window_l2(a.occ + (size_t)de_seg(e8[j]) * 32u, home8[j] >> 3);
   }
 #pragma unroll
   for (int j = 0; j < kPer; ++j) {
-    const uint32_t win = __builtin_amdgcn_alignbit(occw[2 * j + 1], occw[2 * j], (home8[j] * 4u) & 31u);
+    const uint32_t win = owin[j] = window_bits(ow[j], home8[j]);
     const uint32_t ff = ~win ? (uint32_t)__builtin_ctz(~win) : 32u;  // first free slot of the window
     nl[j] = pq[j] ? (ff + 3u) >> 2 : 0u;
   }
@@ -3564,31 +3574,65 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
   // header, the stat slots, the overflow count and the fixed sub-directory slot
   PreRecs pr;
   constexpr int kCpLd = (int)(kPartSubs * kCpPre / (64 * kCpWaves));  // staging loads per thread
+  constexpr int kCpLd1 = (int)(kPartSubs * kCpPre1 / (64 * kCpWaves));  // those of the first stage
   static_assert(kCpLd <= kPre, "the staging loads use the prefetch registers");
-  if constexpr (CP) {
-    // the workgroup stages kCpPre records of each sub-region (slot t of the
-    // workgroup: sub-region t / kCpPre); a wave's loads land below
-    const uint64_t rb0 = (uint64_t)pb * a.cap;
-#pragma unroll
-    for (int u = 0; u < kCpLd; ++u) {
-      const uint32_t t = (uint32_t)u * 64u * kCpWaves + threadIdx.x;
-      const uint64_t j = rb0 + (uint64_t)(t / kCpPre) * a.capx + min(t % kCpPre, a.capx - 1u);
-      pr.op[u] = a.rop[j];
-      const ulonglong2 kv = a.rkv[j];
-      pr.k[u] = kv.x;
-      pr.v[u] = kv.y;
-    }
-  } else {
-    prefetch_records(a, pb, 0, pr);
-  }
-  const uint32_t csub = sub_count_load(a, pb);
+  static_assert(kCpLd1 * 64 * kCpWaves == kPartSubs * kCpPre1 && (kCpLd - kCpLd1) * 64 * kCpWaves == kPartSubs * (kCpPre - kCpPre1),
+                "whole loads per stage");
+  // staging slot (sub-region * kCpPre + record) of this thread's load u: the
+  // first stage covers records [0, kCpPre1) of every sub-region, the second
+  // [kCpPre1, kCpPre) -- wave v those of sub-region v, one per lane
+  const auto cp_slot = [&](int u) -> uint32_t {
+    const uint32_t t = (uint32_t)u * 64u * kCpWaves + threadIdx.x;
+    if (u < kCpLd1) return (t / kCpPre1) * kCpPre + t % kCpPre1;
+    const uint32_t r = t - kPartSubs * kCpPre1;
+    return (r / (kCpPre - kCpPre1)) * kCpPre + kCpPre1 + r % (kCpPre - kCpPre1);
+  };
+  const auto cp_load = [&](int u) {
+    const uint32_t s = cp_slot(u);
+    const uint64_t j = (uint64_t)pb * a.cap + (uint64_t)(s / kCpPre) * a.capx + min(s % kCpPre, a.capx - 1u);
+    pr.op[u] = a.rop[j];
+    const ulonglong2 kv = a.rkv[j];
+    pr.k[u] = kv.x;
+    pr.v[u] = kv.y;
+  };
+  // (the counts and the other small loads first, the records after them:
+  // loads are waited for in issue order, so the second staging stage waits
+  // for the counts with the records still in flight)
   const uint64_t wsv = lane < 7u ? a.wstat[(size_t)w * kWStat + lane] : 0ULL;
   const uint32_t* fslot = a.pool + (size_t)w * kFixedSlot;
   const uint32_t spec0 = (a.pfix && (WIDE || lane < 32u)) ? ld_u32_l2(fslot + lane) : 0u;
   const uint32_t spec1 = (WIDE && a.pfix) ? ld_u32_l2(fslot + 64u + lane) : 0u;
-  const uint64_t hd = a.hdr[w];
+  uint64_t hd = a.hdr[w];
+  uint32_t novf = *a.ovf;
+  uint32_t craw = sub_count_issue(a, pb);
+  if constexpr (CP) {
+    // the workgroup stages its partition bucket's records; a wave's loads
+    // land below.  First stage: unconditional, before anything is known
+#pragma unroll
+    for (int u = 0; u < kCpLd1; ++u) cp_load(u);
+    // (the empty asm statements pin the first use of a small load's value --
+    // its wait -- behind the loads above it: the counts' here, the header's
+    // and the overflow count's after the second stage)
+    asm volatile("" : "+v"(craw));
+  } else {
+    prefetch_records(a, pb, 0, pr);
+  }
+  const uint32_t csub = min(craw, a.capx);
+  // second staging stage: the counts have arrived, the first stage is in flight
+  bool live2 = false;
+  if constexpr (CP && kCpLd1 < kCpLd) {
+    static_assert(kCpLd - kCpLd1 == 1 && kCpPre - kCpPre1 == 64, "wave v loads the second stage of sub-region v");
+    const uint32_t cv = (uint32_t)__builtin_amdgcn_readlane((int)csub, (int)(w & (kCpWaves - 1)));
+    live2 = kCpPre1 + lane < cv;
+    if (live2) cp_load(kCpLd1);
+  }
+  if constexpr (CP) {
+    uint32_t hl = (uint32_t)hd, hh = (uint32_t)(hd >> 32);
+    asm volatile("" : "+v"(hl), "+v"(hh), "+v"(novf));
+    hd = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hh) << 32 | (uint32_t)__builtin_amdgcn_readfirstlane((int)hl);
+    novf = (uint32_t)__builtin_amdgcn_readfirstlane((int)novf);
+  }
   const uint32_t off = hdr_off(hd), db = hdr_db(hd);
-  const uint32_t novf = *a.ovf;
   // the sub-directory, one (two) entries per lane (else loads that wait for the header)
   const bool fixed = a.pfix && off == w * kFixedSlot && db <= kFixedBits;
   uint32_t dv0, dv1 = 0u;
@@ -3609,7 +3653,8 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
     // workgroup barriers are reached by every wave, declining or not
 #pragma unroll
     for (int u = 0; u < kCpLd; ++u) {
-      const uint32_t t = (uint32_t)u * 64u * kCpWaves + threadIdx.x;
+      if (u >= kCpLd1 && !live2) continue;  // (a slot nobody wrote is never listed)
+      const uint32_t t = cp_slot(u);
       cpl->st.op[t] = pr.op[u];
       cpl->st.kv[t] = make_ulonglong2(pr.k[u], pr.v[u]);
     }
@@ -3620,16 +3665,25 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
       const uint64_t lt = (1ULL << lane) - 1;
       const uint32_t v = w & (kCpWaves - 1);
       uint16_t* my = cpl->st.idx[v];
-#pragma unroll 4
-      for (uint32_t c = 0; c < kPartSubs * kCpPre / 64; ++c) {
-        const uint32_t t = c * 64u + lane;
-        const uint32_t cs = (uint32_t)__shfl((int)csub, (int)(t / kCpPre));
-        const uint32_t r = cpl->st.op[t];
-        const bool match = t % kCpPre < cs && ((r >> 22) & (kCpWaves - 1)) == v;
-        const uint64_t bal = __ballot(match);
-        const uint32_t idx = m + (uint32_t)__popcll(bal & lt);
-        if (match && idx < C::FC) my[idx] = (uint16_t)t;
-        m += (uint32_t)__popcll(bal);
+      // sub-region by sub-region, its live records only (cs <= kCpPre here)
+      for (uint32_t xs = 0; xs < kPartSubs; ++xs) {
+        const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)csub, (int)xs);
+        uint32_t r[kCpPre / 64];
+#pragma unroll
+        for (uint32_t q = 0; q < kCpPre / 64; ++q) {
+          const uint32_t i = q * 64u + lane;
+          r[q] = i < cs ? cpl->st.op[xs * kCpPre + i] : ~0u;
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < kCpPre / 64; ++q) {
+          if (q * 64u >= cs) break;
+          const uint32_t i = q * 64u + lane;
+          const bool match = i < cs && ((r[q] >> 22) & (kCpWaves - 1)) == v;
+          const uint64_t bal = __ballot(match);
+          const uint32_t idx = m + (uint32_t)__popcll(bal & lt);
+          if (match && idx < C::FC) my[idx] = (uint16_t)(xs * kCpPre + i);
+          m += (uint32_t)__popcll(bal);
+        }
       }
       if (m > C::FC) dec = 1u;
       __builtin_amdgcn_wave_barrier();
@@ -3714,9 +3768,9 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
     for (int j = 0; j < kPer; ++j) bn[j] = pq[j] ? first_sub(j) : 0u;
     if (!dense_bins(S.seen, pq, bn, C::NB)) return 1u;  // (nothing written yet)
   }
-  uint32_t upd[UPS ? kPer : 1], occw[UPS ? 2 * kPer : 1];
+  uint32_t upd[UPS ? kPer : 1], owin[UPS ? kPer : 1];
   if constexpr (UPS) {
-    if (!upsert_probe(a, pq, rk, e8, home8, upd, occw)) return 1u;  // two inserts of one key
+    if (!upsert_probe(a, pq, rk, e8, home8, upd, owin)) return 1u;  // two inserts of one key
   }
   stamp(srow, kBsLoaded, lane == 0);
   WaveStat c;
@@ -3726,7 +3780,7 @@ __device__ __forceinline__ uint32_t apply_fast(const BucketArgs& a, FastLds<WIDE
   };
   if (!fast_claim<C::FC, C::NB, UPS>(a, w, S.sc, nullptr, a.wl_kv + (size_t)w * kCW, a.wl_op + (size_t)w * kCW,
                                      &S.nsplit, &S.nreq, &S.need, LaneOps{rk, rv, rop, pq, e8, home8, x8}, bin, c, srow,
-                                     UPS ? upd : nullptr, UPS ? occw : nullptr))
+                                     UPS ? upd : nullptr, UPS ? owin : nullptr))
     return 1u;
   if (lane == 0) a.wl_n[w] = S.nsplit;  // parked inserts (0: done)
   request_tail(a, w, S.nreq, S.need, db);

@@ -154,6 +154,34 @@ __device__ __forceinline__ uint4 ld_u4_l2(const uint32_t* p) {
 __device__ __forceinline__ uint32_t ld_u32_l2(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Words wi and (wi + 1) % 32 of a 32-word row (an insert's occupancy window),
+// with ld_u32_l2's cache policy, as one 64-bit register pair that the loads
+// write directly: nothing is computed next to them (it would be waited for
+// there, one insert's window after the other), and window_words /
+// window_bits take the pair apart at the first use.
+// PMDFC_OCC_X2=1 (A/B builds): one 8-byte load takes both words unless wi is
+// 31 (a global dwordx2 load needs its address 4-byte aligned only, and the two
+// words are independent: no atomicity is asked of the pair).  Measured in
+// round 13 and not kept: half the load lanes, no time gained.
+#ifndef PMDFC_OCC_X2
+#define PMDFC_OCC_X2 0
+#endif
+struct WinLd {
+  uint64_t v;  // word wi | word (wi + 1) % 32 << 32
+};
+__device__ __forceinline__ WinLd ld_window_l2(const uint32_t* row, uint32_t wi) {
+  if (PMDFC_OCC_X2 && wi < 31u)
+    return {__hip_atomic_load(reinterpret_cast<const uint64_t*>(row + wi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
+  return {ld_u32_l2(row + wi) | (uint64_t)ld_u32_l2(row + ((wi + 1u) & 31u)) << 32};
+}
+__device__ __forceinline__ uint2 window_words(const WinLd& r, uint32_t) {
+  return make_uint2((uint32_t)r.v, (uint32_t)(r.v >> 32));
+}
+// bit t: slot 4 * line + t (cyclic) of the row is taken -- the 32-slot window of home line `line`
+__device__ __forceinline__ uint32_t window_bits(const WinLd& r, uint32_t line) {
+  const uint2 w = window_words(r, line >> 3);
+  return __builtin_amdgcn_alignbit(w.y, w.x, (line * 4u) & 31u);
+}
 
 // first free slot of the 32-slot window starting at w (a multiple of 4) in a
 // 1024-bit occupancy map, cyclic (CCEH_hybrid.cpp:143-156: (y+i) % kNumSlot);
