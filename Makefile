@@ -5,7 +5,7 @@ CSRC := pmdfc_amd/csrc
 LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/cceh_engine.hip
+SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/cceh_engine.hip
 HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h $(CSRC)/packed_image.h include/pmdfc_cceh.h
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
@@ -16,8 +16,9 @@ FRONTBENCH := $(LIBDIR)/bench_frontend
 IMGKVTEST := $(LIBDIR)/test_gpu_image_kv
 BFKVTEST := $(LIBDIR)/test_gpu_filter_kv
 PAKKVTEST := $(LIBDIR)/test_gpu_packed_kv
+ERASEKVTEST := $(LIBDIR)/test_gpu_erase_kv
 
-all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(FRONTBENCH) oracle
+all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(ERASEKVTEST) $(FRONTBENCH) oracle
 
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(LIBDIR)/obj
@@ -40,6 +41,9 @@ $(BFKVTEST): tests/cpp/test_gpu_filter_kv.cpp $(HOSTLIB)
 
 $(PAKKVTEST): tests/cpp/test_gpu_packed_kv.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_packed_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
+
+$(ERASEKVTEST): tests/cpp/test_gpu_erase_kv.cpp $(HOSTLIB)
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_erase_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(FRONTBENCH): tools/bench_frontend.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tools/bench_frontend.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'

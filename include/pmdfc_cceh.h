@@ -73,7 +73,11 @@ extern "C" {
  * pmdfc_cceh_restore, after which it splits again.  pmdfc_cceh_stats_t.segments
  * is the number of segments in the directory, never more than max_segments:
  * ids counted past the arena's end, and ids retired empty because the pool
- * denied their split after they were taken, are not in it. */
+ * denied their split after they were taken, are not in it.
+ * pmdfc_cceh_erase does not undo it: Erase frees slots, which later Inserts
+ * take through the occupancy words, but it never merges segments or returns
+ * ids to the arena, and "the table stopped splitting" stays sticky across it
+ * as well -- a window that is full after the erases still answers CAPACITY. */
 #define PMDFC_ST_FILTERED 7      /* bloom-negative: miss without an index probe */
 #define PMDFC_ST_WRONG_SHARD 8   /* key's hash prefix is owned by another shard */
 #define PMDFC_ST_ROUTE_OVERFLOW 9 /* routed batch: the owner's carry was full (carry_cap ops waiting), op not applied */
@@ -86,6 +90,7 @@ extern "C" {
                                      error_flags bit 16 is set when it occurs. */
 #define PMDFC_ST_UPDATED 11       /* Insert in upsert mode (PMDFC_CFG_UPSERT): the key was already
                                      in its window; its value was overwritten in place */
+#define PMDFC_ST_ERASED 12        /* Erase: one or more copies of the key were removed */
 
 /* pmdfc_cceh_config_t.flags */
 #define PMDFC_CFG_UPSERT 1u       /* last-writer-wins Insert: the reference's Insert
@@ -181,6 +186,30 @@ int pmdfc_cceh_get_batches(pmdfc_cceh_t* t, const uint64_t* d_keys, uint64_t* d_
  * wave reads the whole 16 KiB segment per key.  Never synchronises. */
 int pmdfc_cceh_find_anyway(pmdfc_cceh_t* t, const uint64_t* d_keys, uint64_t* d_values_out,
                            uint8_t* d_status, uint64_t n, void* stream);
+/* Erase x n: every stored copy of each key is removed.  The
+ * reference has no counterpart (its Delete is a stub, CCEH_hybrid.cpp:322-324);
+ * the contract is the serial rule.  Erase(key) repeats until the probe misses:
+ * probe the key's 32-slot window in probe order up to the first empty slot;
+ * at the first match p, shift back -- among the slots p+1 .. p+31 (cyclic) up
+ * to the first empty one, the first entry whose own window starts at or
+ * before p moves to p and leaves the hole where it was, and so on until no
+ * entry qualifies; then the hole becomes {INVALID, 0} and its occupancy bit
+ * is cleared.  So after every Erase each stored entry again has no empty slot
+ * between its window's start and itself (what every probe's early exit, the
+ * split replay and the mixed batches' early answers rely on), copies of one
+ * key keep their probe order, and a later Get of the key misses.
+ * A batch equals its ops applied one by one in batch order, whatever way a
+ * stream is cut into batches.  d_status per op: PMDFC_ST_ERASED (one or more
+ * copies removed), PMDFC_ST_MISS (not stored at its turn: never stored, or
+ * erased earlier in the batch), PMDFC_ST_RESERVED_KEY, PMDFC_ST_WRONG_SHARD.
+ * n <= max_batch, else PMDFC_ERR_ARG.  Enqueues on `stream` and never
+ * synchronises, except that the first call allocates its scratch.  It frees
+ * slots and nothing else: segments are never merged, capacity, depth and the
+ * directory stay, Utilization falls (see PMDFC_ST_CAPACITY).  Like snapshot it
+ * must not run beside the serving waves.  A batch that repeats one stored key
+ * n times is applied by one wave as a run of n ops: slow but correct.  A
+ * tripped loop guard of the shift (never seen) sets error_flags bit 17. */
+int pmdfc_cceh_erase(pmdfc_cceh_t* t, const uint64_t* d_keys, uint8_t* d_status, uint64_t n, void* stream);
 /* Interleaved Insert/Get in batch order; a Get observes exactly the inserts
  * before it in the batch.  d_values_in is read for inserts, d_values_out is
  * written for gets (0 for inserts and misses).  Small and medium batches take

@@ -74,6 +74,19 @@ int64_t pmdfc_kv_ops(pmdfc_kv_t* kv, const uint8_t* ops, const uint64_t* keys, c
  * flood hand-off, pmdfc_kv_config_t.flood_ops). */
 int64_t pmdfc_kv_ops_async(pmdfc_kv_t* kv, const uint8_t* ops, const uint64_t* keys, const uint64_t* values_in,
                            uint64_t* values_out, uint8_t* status, uint64_t n, uint64_t* places_out);
+/* Removal (pmdfc_cceh_erase: every stored copy of the key goes; the reference's
+ * Delete is a stub and stays one in the facades).  Not a ring op: both calls
+ * run after every queued op with the serving waves stopped, which start again
+ * when ops wait -- a per-op erase pays a stop and a start of the waves, bulk
+ * invalidation goes through pmdfc_kv_erase_run (one stop for n keys, applied in
+ * order).  status: PMDFC_ST_ERASED, PMDFC_ST_MISS, PMDFC_ST_RESERVED_KEY, or
+ * 0xFF for a key that could not be served.  An attached counting BF loses one
+ * count per key answered ERASED (a key stored c > 1 times leaves c - 1 counts:
+ * a stale positive, removed by pmdfc_kv_rebuild_cbf).  pmdfc_kv_erase returns
+ * PMDFC_ERR_STATE for status 0xFF; pmdfc_kv_erase_run the number of such keys
+ * (>= 0), or < 0 on an argument error. */
+int pmdfc_kv_erase(pmdfc_kv_t* kv, uint64_t key, uint8_t* status);
+int64_t pmdfc_kv_erase_run(pmdfc_kv_t* kv, const uint64_t* keys, uint8_t* status, uint64_t n);
 /* wait for every op queued before the call */
 int pmdfc_kv_flush(pmdfc_kv_t* kv);
 

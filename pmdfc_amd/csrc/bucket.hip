@@ -378,9 +378,10 @@ __device__ __forceinline__ void wave_sort32_lds(uint32_t* buf, uint32_t n, uint3
 // order 0..1023; each entry goes to child (hash bit 63-L) at the first free
 // slot of its own 32-slot window, or is dropped if that window is full.
 //
-// Cluster decomposition (exact).  Nothing is ever deleted, so an
-// entry at parent slot s with window start w has every slot of [w, s]
-// occupied: it lies in one CLUSTER (maximal run of occupied
+// Cluster decomposition (exact).  Inserts never free a slot, and
+// slots are freed only by Erase, which restores this before it returns
+// (erase.hip): an entry at parent slot s with window start w has every slot
+// of [w, s] occupied, so it lies in one CLUSTER (maximal run of occupied
 // parent slots).  Replaying in slot order, every entry lands in [w, s]: all
 // entries before it landed at or before their own slots.  So clusters replay
 // independently, each by one lane with its two child bitmaps in registers.
@@ -1089,9 +1090,10 @@ struct RunCtx {  // what one run needs (passed by value: no kernarg copies)
 // the slot of `key` in its window if the key is stored there, else -1.  The
 // probe walks the occupied prefix of the window (the bitmap marks claims of
 // this run too; their slots still read INVALID in memory, which never
-// matches), one 64-B line at a time with its 4 pairs loaded together.  With no
-// deletes no stored entry sits past the window's first free slot,
-// so the first free slot ends the probe, as in the reference's claim order.
+// matches), one 64-B line at a time with its 4 pairs loaded together.  No
+// stored entry sits past the window's first free slot (slots are
+// freed only by Erase, which restores that before it returns, erase.hip), so
+// the first free slot ends the probe, as in the reference's claim order.
 __device__ __forceinline__ int upsert_find(const ulonglong2* sp, const uint32_t* bm, uint32_t wi0, uint64_t key) {
   for (uint32_t l = 0; l < kLines; ++l) {
     const uint32_t s0 = (wi0 + 4u * l) & (kSlots - 1);  // line aligned: its 4 bits share a word
@@ -3443,7 +3445,8 @@ struct FastLds {
 // UPS: last-writer-wins (PMDFC_CFG_UPSERT): a bucket with two inserts of one
 // key goes to the general pass; otherwise each insert's window is probed for
 // its key over the occupied prefix (a stored key lies before the window's
-// first free slot: nothing is deleted) and a stored key is overwritten.
+// first free slot: slots are freed only by Erase, which restores that before
+// it returns, erase.hip) and a stored key is overwritten.
 // The coarse-partition first pass (k_apply_fast_cp): k_part partitions into
 // 2^(p1 - 3) buckets, each the records of 8 directory buckets, so a tile's run
 // per partition bucket is ~8 records (whole 128-B lines, 1/8 of the reserve
@@ -3500,7 +3503,8 @@ __device__ __forceinline__ bool dense_bins(uint32_t* seen, const bool (&pq)[kPer
 
 // The lean pass in last-writer-wins mode: each insert's window is probed for
 // its key over the occupied prefix (a stored key lies before the window's
-// first free slot: nothing is deleted).  upd[j]: the slot of insert j's key
+// first free slot: slots are freed only by Erase, which restores that before
+// it returns).  upd[j]: the slot of insert j's key
 // (0xFFFF: absent); owin[j]: its window's occupancy bits (window_bits), for
 // fast_claim.  False: two inserts of one key, nothing probed (the general
 // pass takes the bucket).

@@ -201,7 +201,10 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
 
 // Quad-cooperative Get probe (4 lanes per key, one 16-B slot each, one 64-B
 // line per step, early exit at the first empty slot -- SURVEY a5, equal to the
-// reference's full scan CCEH_hybrid.cpp:372-382 because nothing is deleted).
+// reference's full scan CCEH_hybrid.cpp:372-382 because no stored entry has an
+// empty slot between its window's start and itself: inserts never free a
+// slot, and slots are freed only by Erase, which restores that invariant
+// before it returns, erase.hip).
 // All 4 lanes of the quad must call it with the same key/h.  Returns HIT/MISS,
 // *val valid on every lane of the quad, *lines = 64-B lines read.
 // From an even window line, the next line is the other half of the same
@@ -240,8 +243,9 @@ __device__ __forceinline__ uint8_t quad_probe(const ulonglong2* __restrict__ seg
 
 // quad_probe that also tells a single copy of the key from several: scans
 // on to the window's first empty slot (every copy of a key lies before it:
-// slots are never freed, and an Insert takes the first free slot of its
-// window, CCEH_hybrid.cpp:143-168; split replay keeps that).  Returns 0 miss,
+// an Insert takes the first free slot of its window, CCEH_hybrid.cpp:143-168,
+// split replay keeps that, and slots are freed only by Erase, which closes
+// the gap before it returns, erase.hip).  Returns 0 miss,
 // 1 hit with exactly one copy, 2 several copies.  Lines in pairs as above.
 __device__ __forceinline__ uint8_t quad_probe_once(const ulonglong2* __restrict__ seg, uint64_t key,
                                                    uint64_t h, uint32_t q, uint64_t* val) {

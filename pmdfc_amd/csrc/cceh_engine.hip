@@ -281,6 +281,17 @@ struct pmdfc_cceh {
   uint32_t* gflat_bits = nullptr;  // its physical depth (device)
   bool flat_valid = false;         // host: no insert since the last flatten
 
+  // Erase batches (erase.hip): five rows of max_batch words (segment ids and
+  // batch indices before and after the sort, the run heads), the runs' cursor
+  // and the sort's temporary storage; allocated by the first Erase
+  struct Erase {
+    uint32_t* rows = nullptr;
+    uint32_t* cursor = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    uint32_t sort_bits = 0;
+  } er;
+
   Geo geo() const { return Geo{hdr, pool, p1, sbits, shard, nullptr, nullptr}; }
   Geo geo_flat() const { return Geo{hdr, pool, p1, sbits, shard, gflat, gflat_bits}; }
 };
@@ -1035,6 +1046,55 @@ int pmdfc_cceh_find_anyway(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* vout
   DevGuard g(t->dev);
   launch_find_anyway(keys, vout, st, n, t->geo(), t->pairs, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
+
+// Erase x n (erase.hip): probe, stable sort by segment, run
+// heads, one wave per run.  Only the first call waits (it allocates the scratch).
+int pmdfc_cceh_erase(pmdfc_cceh_t* t, const uint64_t* keys, uint8_t* st, uint64_t n, void* stream) {
+  if (!t || (n && (!keys || !st))) return fail(PMDFC_ERR_ARG, "null argument");
+  if (n > t->max_batch) return fail(PMDFC_ERR_ARG, "n > max_batch");
+  if (n == 0) return PMDFC_OK;
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  pmdfc_cceh::Erase& er = t->er;
+  if (!er.rows) {
+    er.sort_bits = ceil_log2(t->max_segs) + 1;
+    HIPCHK(erase_sort_temp_bytes(t->max_batch, er.sort_bits, &er.tmp_bytes));
+    void *rows = nullptr, *tmp = nullptr;
+    HIPCHK(hipMalloc(&rows, (5ull * t->max_batch + 1) * sizeof(uint32_t)));
+    t->dev_allocs.push_back(rows);
+    HIPCHK(hipMalloc(&tmp, std::max<size_t>(er.tmp_bytes, 16)));
+    t->dev_allocs.push_back(tmp);
+    er.cursor = static_cast<uint32_t*>(rows) + 5ull * t->max_batch;
+    er.tmp = tmp;
+    er.rows = static_cast<uint32_t*>(rows);
+  }
+  if (!t->flat_valid) {  // (as do_get)
+    launch_flatten(t->hdr, t->pool, t->p1, t->gflat, t->gflat_bits, t->kn.flat_max, s);
+    t->flat_valid = true;
+  }
+  EraseArgs a{};
+  a.keys = keys;
+  a.st = st;
+  a.n = n;
+  a.g = t->geo_flat();
+  a.pairs = t->pairs;
+  a.occ = t->occ;
+  a.ctl = t->ctl;
+  a.max_segs = (uint32_t)t->max_segs;
+  const uint64_t mb = t->max_batch;
+  a.seg_in = er.rows;
+  a.seg_out = er.rows + mb;
+  a.idx_in = er.rows + 2 * mb;
+  a.idx_out = er.rows + 3 * mb;
+  a.work = er.rows + 4 * mb;
+  a.cursor = er.cursor;
+  a.tmp = er.tmp;
+  a.tmp_bytes = er.tmp_bytes;
+  a.sort_bits = er.sort_bits;
+  HIPCHK(launch_erase(a, s));
   return PMDFC_OK;
 }
 

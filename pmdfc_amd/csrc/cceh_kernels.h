@@ -468,6 +468,35 @@ constexpr uint32_t kCbfScanBlocks = 2048;  // the loop's grid: 8 workgroups of f
 void launch_cbf_scan(bool audit, const ulonglong2* pairs, const DevCtl* ctl, uint64_t max_segs, uint8_t* cnt,
                      uint64_t m, uint32_t k, unsigned long long* out, hipStream_t s);
 
+// erase.hip (batched key removal).  One Erase batch: the
+// probe writes the final statuses of the ops that remove nothing and each
+// hit's arena segment id into seg_in (max_segs for the others); a stable radix
+// sort of {segment id, batch index} over sort_bits bits brings every
+// segment's ops together in batch order; the heads of the runs are listed in
+// work (their count in *cursor); one wave per run applies its ops in order.
+constexpr uint32_t kErrEraseGuard = 1u << 17;  // DevCtl::err: a loop guard of k_erase_apply tripped
+struct EraseArgs {
+  const uint64_t* keys;  // n
+  uint8_t* st;           // n
+  uint64_t n;            // <= max_batch
+  Geo g;                 // with the flat directory
+  ulonglong2* pairs;
+  uint32_t* occ;
+  DevCtl* ctl;
+  uint32_t max_segs;
+  // the scratch of the handle, each row max_batch entries
+  uint32_t *seg_in, *seg_out;  // per op / sorted: the segment id
+  uint32_t *idx_in, *idx_out;  // per op / sorted: the batch index
+  uint32_t* work;              // sorted positions of the run heads
+  uint32_t* cursor;            // their count
+  void* tmp;                   // the sort's temporary storage
+  size_t tmp_bytes;
+  uint32_t sort_bits;          // ceil_log2(max_segs) + 1
+};
+// temporary storage of the sort for batches of at most max_batch ops
+hipError_t erase_sort_temp_bytes(uint64_t max_batch, uint32_t sort_bits, size_t* bytes);
+hipError_t launch_erase(const EraseArgs& a, hipStream_t s);
+
 // trace.hip (replay_KV trace ingestion)
 struct TraceLine {
   uint64_t key;  // (inode << 32) + offset

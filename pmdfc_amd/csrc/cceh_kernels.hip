@@ -262,7 +262,8 @@ __global__ __launch_bounds__(256) void k_mixed_prep(const MixedArgs a) {
 // answered WITHOUT asking whether the batch inserts the key again (early 3):
 // every slot of a window before a stored entry, in probe order, is occupied
 // (an entry is placed at the first free slot, by Insert and by Split's replay
-// alike, and nothing is ever deleted), so a new copy lands after the old one;
+// alike, and slots are freed only by Erase, which restores exactly this before
+// it returns, erase.hip), so a new copy lands after the old one;
 // and a split replays a non-wrapping window in slot order = probe order,
 // placing every entry at the first free slot, so two copies keep their order
 // (the later one's slot is past the earlier one's) and a dropped copy drops

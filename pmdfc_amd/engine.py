@@ -30,7 +30,7 @@ OP_GET, OP_INSERT = 0, 1
 PMDFC_ERR_SIZE = -5  # an output buffer is smaller than the result (include/pmdfc_cceh.h)
 CBF_KEEP = 1  # PMDFC_CBF_KEEP: pmdfc_cbf_rebuild adds to what the filter holds
 (ST_MISS, ST_HIT, ST_INSERTED, ST_RESERVED_KEY, ST_UNSPLITTABLE, ST_DEPTH_LIMIT, ST_CAPACITY,
- ST_FILTERED, ST_WRONG_SHARD, ST_ROUTE_OVERFLOW, ST_SPLIT_LOST, ST_UPDATED) = range(12)
+ ST_FILTERED, ST_WRONG_SHARD, ST_ROUTE_OVERFLOW, ST_SPLIT_LOST, ST_UPDATED, ST_ERASED) = range(13)
 CFG_UPSERT = 1  # pmdfc_cceh_config_t.flags: last-writer-wins Insert
 K_NAMES = ["get", "prep", "route", "final", "process", "split", "parked", "mixed_get", "bloom"]
 
@@ -89,6 +89,7 @@ EXPORTS = [
     "pmdfc_cceh_snapshot", "pmdfc_cceh_restore",
     "pmdfc_cceh_snapshot_packed", "pmdfc_cceh_export_entries", "pmdfc_cceh_packed_scan_block",
     "pmdfc_cbf_rebuild", "pmdfc_cbf_audit",
+    "pmdfc_cceh_erase",
 ]
 
 
@@ -188,6 +189,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_cceh_snapshot_packed": (i32, [P, P, u64, C.POINTER(u64), P]),
         "pmdfc_cceh_export_entries": (i32, [P, P, P, u64, C.POINTER(u64), P]),
         "pmdfc_cceh_packed_scan_block": (u32, []),
+        "pmdfc_cceh_erase": (i32, [P, P, P, u64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -474,9 +476,26 @@ class CCEH:
 
     def Delete(self, keys):
         """CCEH::Delete is an unimplemented stub returning false
-        (CCEH_hybrid.cpp:322-324); kept for interface parity."""
+        (CCEH_hybrid.cpp:322-324); kept for interface parity.  Erase removes
+        keys."""
         n = len(keys)
         return np.zeros(n, dtype=bool)
+
+    def Erase(self, keys):
+        """Remove every stored copy of each key (pmdfc_cceh_erase), in batch
+        order.  Returns the statuses: ST_ERASED, ST_MISS for a key not stored
+        at its turn, ST_RESERVED_KEY, ST_WRONG_SHARD.  Freed slots are taken
+        by later Inserts; segments are never merged, so Capacity stays and
+        Utilization falls.  More than max_batch keys go as consecutive
+        batches, which gives the same table and statuses as one."""
+        dev_in = isinstance(keys, torch.Tensor)
+        k = self._d.u64(keys)
+        st = torch.empty(k.numel(), dtype=torch.uint8, device=self._d.device)
+        for off in range(0, k.numel(), self.max_batch):
+            m = min(self.max_batch, k.numel() - off)
+            _check(load_library().pmdfc_cceh_erase(self._h, k[off:].data_ptr(), st[off:].data_ptr(), m,
+                                                   self._d.stream()), "pmdfc_cceh_erase")
+        return st if dev_in else _host_out(st, "u8")
 
     def Recovery(self) -> bool:
         """CCEH::Recovery (CCEH_hybrid.cpp:391-410) repairs directory entries of

@@ -194,6 +194,7 @@ void BatchCore::release() {
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   if (sync_) (void)hipStreamSynchronize((hipStream_t)sync_);
   if (fa_dev_) (void)hipFree(fa_dev_);
+  if (er_dev_) (void)hipFree(er_dev_);
   if (fl_h_in_) (void)hipHostFree(fl_h_in_);
   if (fl_h_out_) (void)hipHostFree(fl_h_out_);
   if (fl_d_in_) (void)hipFree(fl_d_in_);
@@ -204,7 +205,7 @@ void BatchCore::release() {
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
   if (sync_) (void)hipStreamDestroy((hipStream_t)sync_);
   if (t_) pmdfc_cceh_destroy(t_);
-  fa_dev_ = nullptr, fl_h_in_ = fl_h_out_ = fl_d_in_ = fl_d_out_ = nullptr;
+  fa_dev_ = nullptr, er_dev_ = nullptr, fl_h_in_ = fl_h_out_ = fl_d_in_ = fl_d_out_ = nullptr;
   req_ = nullptr, resp_ = nullptr, ctl_ = nullptr, stream_ = sync_ = nullptr, t_ = nullptr;
 }
 
@@ -1016,6 +1017,68 @@ uint8_t BatchCore::FindAnyway(uint64_t key, uint64_t* value) {
       }))
     return kBatchFailed;
   return status;
+}
+
+// ---------------------------------------------------------------- removal
+
+// (inside with_engine) Engine batches of at most er_cap_ keys, in order; after
+// each, the keys it answered ERASED leave the attached filter once each, in
+// batch order (compacted on the host: the statuses come back anyway).
+uint64_t BatchCore::erase_batches(void* stream, const uint64_t* keys, uint8_t* status, uint64_t n) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!er_dev_) {
+    er_cap_ = std::max<uint32_t>(cfg_.max_batch, 64);  // (the engine's max_batch, init)
+    if (hipMalloc((void**)&er_dev_, er_cap_ * 18) != hipSuccess) {
+      er_dev_ = nullptr;
+      set_error("Erase: out of device memory");
+      return 0;
+    }
+  }
+  uint64_t* dk = reinterpret_cast<uint64_t*>(er_dev_);
+  uint64_t* dgone = dk + er_cap_;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(dgone + er_cap_);
+  uint8_t* dbf = dst + er_cap_;
+  std::vector<uint64_t> gone;
+  for (uint64_t o = 0; o < n; o += er_cap_) {
+    const uint64_t m = std::min<uint64_t>(er_cap_, n - o);
+    int rc = PMDFC_OK;
+    bool ok = hipMemcpyAsync(dk, keys + o, m * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
+              (rc = pmdfc_cceh_erase(t_, dk, dst, m, st)) == PMDFC_OK &&
+              hipMemcpyAsync(status + o, dst, m, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              hipStreamSynchronize(st) == hipSuccess;
+    if (ok && bf_) {
+      gone.clear();
+      for (uint64_t i = 0; i < m; ++i)
+        if (status[o + i] == PMDFC_ST_ERASED) gone.push_back(keys[o + i]);
+      if (!gone.empty())
+        ok = hipMemcpyAsync(dgone, gone.data(), gone.size() * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
+             (rc = pmdfc_cbf_delete(bf_, dgone, dbf, gone.size(), st)) == PMDFC_OK &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) {
+      set_error(std::string("Erase: ") + (rc != PMDFC_OK ? pmdfc_last_error() : "HIP call failed"));
+      return o;
+    }
+  }
+  return n;
+}
+
+uint64_t BatchCore::EraseRun(const uint64_t* keys, uint8_t* status, uint64_t n) {
+  if (n == 0) return 0;
+  uint64_t done = 0;
+  with_engine([&](hipStream_t st) { done = erase_batches(st, keys, status, n); });
+  for (uint64_t i = done; i < n; ++i) status[i] = kBatchFailed;
+  if (done < n) {
+    failed_.fetch_add(n - done);
+    fail_by_st_[kBatchFailed].fetch_add(n - done);
+  }
+  return n - done;
+}
+
+uint8_t BatchCore::Erase(uint64_t key) {
+  uint8_t st = kBatchFailed;
+  EraseRun(&key, &st, 1);
+  return st;
 }
 
 int BatchCore::Stats(pmdfc_cceh_stats_t* out) {

@@ -38,8 +38,9 @@
 // post its reply from a completion) uses InsertAsync / GetAsync: the op is
 // queued and a callback runs on the control thread when its result is back.
 //
-// Calls that need the whole engine (Utilization, Capacity, FindAnyway, the
-// counting-BF pack, attach, rebuild and audit, Save and Load) wait for every
+// Calls that need the whole engine (Utilization, Capacity, FindAnyway, Erase
+// and EraseRun, the counting-BF pack, attach, rebuild and audit, Save and
+// Load) wait for every
 // op queued before them, stop the device wave, run on the engine's stream,
 // and start it again.
 //
@@ -148,6 +149,23 @@ class BatchCore {
   // wait until every op enqueued before this call has completed (false, and
   // no wait, from a completion callback)
   bool flush();
+
+  // ---- removal (pmdfc_cceh_erase: every stored copy of the key goes).  Not a
+  // ring op: both calls run after every op enqueued so far, with the waves
+  // stopped, on the synchronous stream, and the control thread starts the
+  // waves again when ops wait -- so a per-op Erase costs a stop and a start
+  // of the waves, and bulk invalidation belongs in EraseRun (one stop for the
+  // whole run, engine batches of at most max_batch keys, in order).  Status
+  // per key: PMDFC_ST_ERASED, PMDFC_ST_MISS, PMDFC_ST_RESERVED_KEY, or
+  // kBatchFailed (a failed HIP or engine call; from a completion callback at
+  // once, nothing applied).  With a counting BF attached, each key answered
+  // ERASED is deleted from it once (pmdfc_cbf_delete, in batch order, under
+  // the same stop).  A key that was stored c > 1 times (duplicates without
+  // upsert) so leaves c - 1 counts behind: a stale positive, never a false
+  // negative; RebuildCountingBF removes it.  EraseRun returns the number of
+  // keys answered kBatchFailed.
+  uint8_t Erase(uint64_t key);
+  uint64_t EraseRun(const uint64_t* keys, uint8_t* status, uint64_t n);
 
   // ---- counting BF of KV (server/KV.cpp:113-121).  The filter must live on
   // the same device and outlive the core's use of it.
@@ -296,6 +314,8 @@ class BatchCore {
   bool with_engine(F f);  // flush, stop the waves, f(stream), start them again
   int save_image(const char* path, bool packed);  // Save / SavePacked
   int rebuild_bf(void* stream, uint64_t* stored);  // (inside with_engine) rebuild + pack + one sync
+  // (inside with_engine) keys [0, n) erased in engine batches; returns the keys before the first failed batch
+  uint64_t erase_batches(void* stream, const uint64_t* keys, uint8_t* status, uint64_t n);
 
   pmdfc_cceh_t* t_ = nullptr;
   pmdfc_cbf_t* bf_ = nullptr;
@@ -329,6 +349,8 @@ class BatchCore {
   alignas(64) std::atomic<uint32_t> rgen_{0};
   std::atomic<int32_t> rwaiters_{0};
   uint64_t* fa_dev_ = nullptr;    // FindAnyway: device {key, value, status}
+  uint8_t* er_dev_ = nullptr;     // EraseRun (allocated by the first): keys, the erased keys, statuses, the filter's answers
+  uint64_t er_cap_ = 0;           // keys per engine batch
   // flood batches: pinned staging (keys, values, ops, cbf ops | values, statuses) and device copies
   uint64_t fl_cap_ = 0;
   uint8_t *fl_h_in_ = nullptr, *fl_h_out_ = nullptr, *fl_d_in_ = nullptr, *fl_d_out_ = nullptr;

@@ -71,9 +71,16 @@ class GpuCCEH : public IHash {
     std::vector<uint8_t> st(ks.size());
     core_.InsertRun(ks.data(), vs.data(), st.data(), ks.size(), /*count_bf=*/false);
   }
-  bool Delete(Key_t& key) override {  // CCEH_hybrid.cpp:322-324 stub
+  bool Delete(Key_t& key) override {  // CCEH_hybrid.cpp:322-324 stub (the drop-in contract); Erase removes
     (void)key;
     return false;
+  }
+  // Removal, which the reference lacks (BatchCore::Erase / EraseRun: after
+  // every queued op, the waves stopped meanwhile; an attached counting BF
+  // loses one count per erased key).  Erase: true iff a copy was removed.
+  bool Erase(Key_t& key) { return core_.Erase(key) == PMDFC_ST_ERASED; }
+  int EraseBatch(const uint64_t* keys, uint8_t* status, uint64_t n) {
+    return core_.EraseRun(keys, status, n) ? PMDFC_ERR_STATE : PMDFC_OK;
   }
   Value_t Get(Key_t& key) override {  // NONE on a miss (and on a failed op)
     uint64_t v = 0;

@@ -52,7 +52,14 @@ class GpuCCEHHybrid : public ICCEH {
     core_.InsertRun(ks.data(), vs.data(), st.data(), ks.size(), /*count_bf=*/false);
   }
   void Insert(Key_t& key, Value_t value) override { core_.Insert(key, reinterpret_cast<uint64_t>(value)); }
-  bool Delete(Key_t&) override { return false; }  // CCEH_hybrid.cpp:322-324 stub
+  bool Delete(Key_t&) override { return false; }  // CCEH_hybrid.cpp:322-324 stub (the drop-in contract); Erase removes
+  // Removal, which the reference lacks (BatchCore::Erase / EraseRun: after
+  // every queued op, the waves stopped meanwhile; an attached counting BF
+  // loses one count per erased key).  Erase: true iff a copy was removed.
+  bool Erase(Key_t& key) { return core_.Erase(key) == PMDFC_ST_ERASED; }
+  int EraseBatch(const uint64_t* keys, uint8_t* status, uint64_t n) {
+    return core_.EraseRun(keys, status, n) ? PMDFC_ERR_STATE : PMDFC_OK;
+  }
   Value_t Get(Key_t& key) override {
     uint64_t v = 0;
     return core_.Get(key, &v) == PMDFC_ST_HIT ? reinterpret_cast<Value_t>(v) : NONE;

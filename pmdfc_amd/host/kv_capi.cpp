@@ -112,6 +112,18 @@ int64_t pmdfc_kv_ops_async(pmdfc_kv_t* kv, const uint8_t* ops, const uint64_t* k
   return bad;
 }
 
+int pmdfc_kv_erase(pmdfc_kv_t* kv, uint64_t key, uint8_t* status) {
+  if (!kv) return PMDFC_ERR_ARG;
+  const uint8_t st = kv->core->Erase(key);
+  if (status) *status = st;
+  return st == pmdfc_host::kBatchFailed ? PMDFC_ERR_STATE : PMDFC_OK;
+}
+
+int64_t pmdfc_kv_erase_run(pmdfc_kv_t* kv, const uint64_t* keys, uint8_t* status, uint64_t n) {
+  if (!kv || (n && (!keys || !status))) return PMDFC_ERR_ARG;
+  return (int64_t)kv->core->EraseRun(keys, status, n);
+}
+
 int pmdfc_kv_flush(pmdfc_kv_t* kv) {
   if (!kv) return PMDFC_ERR_ARG;
   return kv->core->flush() ? PMDFC_OK : PMDFC_ERR_STATE;

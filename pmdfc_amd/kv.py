@@ -32,6 +32,7 @@ KV_EXPORTS = [
     "pmdfc_kv_find_anyway", "pmdfc_kv_stats", "pmdfc_kv_dump", "pmdfc_kv_phase", "pmdfc_kv_last_error",
     "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_save_packed", "pmdfc_kv_load",
     "pmdfc_kv_attach_cbf", "pmdfc_kv_rebuild_cbf", "pmdfc_kv_audit_cbf",
+    "pmdfc_kv_erase", "pmdfc_kv_erase_run",
 ]
 
 _kvlib = None
@@ -75,6 +76,8 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_rebuild_cbf": (i32, [P, C.POINTER(u64)]),
         "pmdfc_kv_audit_cbf": (i32, [P, P]),
         "pmdfc_kv_last_error": (C.c_char_p, [P]),
+        "pmdfc_kv_erase": (i32, [P, u64, P]),
+        "pmdfc_kv_erase_run": (i64, [P, P, P, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -198,6 +201,25 @@ class KV:
 
     def flush(self):
         load_kv_library().pmdfc_kv_flush(self._h)
+
+    # ---- removal (CCEH.Erase); not ring ops: the serving waves stop meanwhile
+    def erase(self, key: int) -> int:
+        """Remove every stored copy of `key`, after every queued op -> its
+        status (ST_ERASED, ST_MISS, ST_RESERVED_KEY; 0xFF if it could not be
+        served).  Stops and restarts the serving waves: use erase_run for many."""
+        st = C.c_uint8()
+        load_kv_library().pmdfc_kv_erase(self._h, key, C.byref(st))
+        return st.value
+
+    def erase_run(self, keys) -> np.ndarray:
+        """erase() of every key in order under one stop of the waves -> the
+        statuses.  An attached counting BF loses one count per erased key."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        st = np.zeros(k.size, np.uint8)
+        rc = load_kv_library().pmdfc_kv_erase_run(self._h, k.ctypes.data, st.ctypes.data, k.size)
+        if rc < 0:
+            self._err("erase_run", rc)
+        return st
 
     def stats(self) -> dict:
         s = Stats()
