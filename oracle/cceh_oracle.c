@@ -22,6 +22,11 @@
  *            evident intent, restated here, is `target->_[loc].key == key`:
  *            the first slot in probe order that is INVALID or holds the key
  *            takes the pair (last-writer-wins, north_star).
+ *   Erase    no reference line: the reference's Delete is a stub (:322-324).
+ *            oc_erase restates the rule of DESIGN.md 4.8 (probe to the first
+ *            empty slot, first match, backward shift, repeat until the probe
+ *            misses); tests/erase_ref.py is that rule's model, and the CPU
+ *            tests hold this restatement to it.
  *
  * Build-contract divergences (documented in DESIGN.md):
  *   - keys INVALID/SENTINEL are rejected (reference: undefined);
@@ -372,6 +377,56 @@ void oc_insert_batch(oc_cceh* t, const uint64_t* keys, const uint64_t* values,
 void oc_get_batch(oc_cceh* t, const uint64_t* keys, size_t n,
                   uint64_t* out_values, uint8_t* out_status) {
   for (size_t i = 0; i < n; ++i) out_status[i] = (uint8_t)oc_get(t, keys[i], &out_values[i]);
+}
+
+/* Erase  DESIGN.md 4.8, "The rule", literally, on this table's segments.  The
+ * reference has none (Delete is a stub, CCEH_hybrid.cpp:322-324): there is no
+ * reference line to cite, and no counter of oc_stats moves. */
+int oc_erase(oc_cceh* t, uint64_t key) {
+  if (key == OC_INVALID || key == OC_SENTINEL) return OC_ST_RESERVED_KEY;
+  const uint64_t h = oc_hash64(key);
+  const uint32_t w = (uint32_t)(h & 0xFF) * 4;
+  oc_pair* seg = seg_ptr(t, t->dir[dir_index(h, t->depth)]);
+  int erased = 0;
+  for (;;) { /* (a window holds at most 32 copies: at most 33 rounds) */
+    /* 1. the window in probe order up to the first empty slot */
+    uint32_t p = OC_SLOTS_PER_SEGMENT;
+    for (uint32_t i = 0; i < OC_PROBE_WINDOW; ++i) {
+      uint32_t j = (w + i) % OC_SLOTS_PER_SEGMENT;
+      if (seg[j].key == OC_INVALID) break;
+      if (seg[j].key == key) {
+        p = j; /* 2. the first match */
+        break;
+      }
+    }
+    if (p == OC_SLOTS_PER_SEGMENT) return erased ? OC_ST_ERASED : OC_ST_MISS;
+    erased = 1;
+    /* 3. backward shift: the hole advances on every step */
+    for (;;) {
+      uint32_t c = OC_SLOTS_PER_SEGMENT;
+      for (uint32_t d = 1; d < OC_PROBE_WINDOW; ++d) {
+        uint32_t j = (p + d) % OC_SLOTS_PER_SEGMENT;
+        if (seg[j].key == OC_INVALID) break;
+        uint32_t wc = (uint32_t)(oc_hash64(seg[j].key) & 0xFF) * 4;
+        /* (c - w_c) mod 1024 >= (c - p) mod 1024: its window starts at or before p */
+        if ((j + OC_SLOTS_PER_SEGMENT - wc) % OC_SLOTS_PER_SEGMENT >= d) {
+          c = j;
+          break;
+        }
+      }
+      if (c == OC_SLOTS_PER_SEGMENT) {
+        seg[p].key = OC_INVALID;
+        seg[p].value = 0;
+        break;
+      }
+      seg[p] = seg[c];
+      p = c;
+    }
+  }
+}
+
+void oc_erase_batch(oc_cceh* t, const uint64_t* keys, size_t n, uint8_t* out_status) {
+  for (size_t i = 0; i < n; ++i) out_status[i] = (uint8_t)oc_erase(t, keys[i]);
 }
 
 uint32_t oc_depth(const oc_cceh* t) { return t->depth; }

@@ -48,6 +48,7 @@ enum {
   OC_ST_CAPACITY = 6,
   OC_ST_FILTERED = 7,
   OC_ST_UPDATED = 11,   /* upsert mode: the key's slot was overwritten */
+  OC_ST_ERASED = 12,    /* oc_erase: one or more copies of the key were removed */
 };
 
 /* ---- hashes ---------------------------------------------------------- */
@@ -98,6 +99,15 @@ void oc_insert_batch(oc_cceh* t, const uint64_t* keys, const uint64_t* values,
                      size_t n, uint8_t* out_status);
 void oc_get_batch(oc_cceh* t, const uint64_t* keys, size_t n,
                   uint64_t* out_values, uint8_t* out_status);
+/* Erase: the serial rule of DESIGN.md 4.8 on this table's segments.  The
+ * reference has no erase (its Delete is a stub, CCEH_hybrid.cpp:322-324), so
+ * this cites the rule, not a reference line; tests/erase_ref.py is the rule's
+ * model and tests/test_churn_ref.py holds this restatement to it.  It exists
+ * for the interleaving of erases with splits and doublings, which the model
+ * (a table that cannot split) cannot follow.  Returns OC_ST_ERASED,
+ * OC_ST_MISS or OC_ST_RESERVED_KEY; the batch form applies the keys in order. */
+int oc_erase(oc_cceh* t, uint64_t key);
+void oc_erase_batch(oc_cceh* t, const uint64_t* keys, size_t n, uint8_t* out_status);
 
 /* introspection */
 uint32_t oc_depth(const oc_cceh* t);

@@ -17,6 +17,7 @@ _LIB = None
 
 ST_MISS, ST_HIT, ST_INSERTED, ST_RESERVED_KEY, ST_UNSPLITTABLE, ST_DEPTH_LIMIT, ST_CAPACITY, ST_FILTERED = range(8)
 ST_UPDATED = 11
+ST_ERASED = 12
 OP_GET, OP_INSERT = 0, 1
 
 
@@ -76,6 +77,9 @@ def lib() -> C.CDLL:
         L.oc_insert_batch.argtypes = [P, u64p, u64p, C.c_size_t, u8p]
         L.oc_get_batch.argtypes = [P, u64p, C.c_size_t, u64p, u8p]
         L.oc_find_anyway_batch.argtypes = [P, u64p, C.c_size_t, u64p, u8p]
+        L.oc_erase.restype = C.c_int
+        L.oc_erase.argtypes = [P, C.c_uint64]
+        L.oc_erase_batch.argtypes = [P, u64p, C.c_size_t, u8p]
         L.oc_depth.restype = C.c_uint32
         L.oc_depth.argtypes = [P]
         L.oc_num_segments.restype = C.c_uint32
@@ -202,6 +206,14 @@ class OracleCCEH:
         st = np.empty(keys.size, dtype=np.uint8)
         lib().oc_mixed(self._t, ops, keys, values, keys.size, out, st)
         return out, st
+
+    def erase(self, keys) -> np.ndarray:
+        """Erase (the reference has none) of each key in order
+        -> statuses ST_ERASED / ST_MISS / ST_RESERVED_KEY."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        st = np.empty(keys.size, dtype=np.uint8)
+        lib().oc_erase_batch(self._t, keys, keys.size, st)
+        return st
 
     @property
     def depth(self) -> int:

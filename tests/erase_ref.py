@@ -15,7 +15,8 @@ model IS the contract:
        p = c, look again; when there is none, write {INVALID, 0} at p.
 
 tests/test_erase_ref.py checks the model's properties on the CPU;
-tests/test_gpu_erase.py checks the engine against the model.
+tests/test_gpu_erase.py checks the engine against the model;
+tests/test_churn_ref.py holds the serial oracle's restatement (oc_erase) to it.
 """
 import numpy as np
 
