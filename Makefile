@@ -5,8 +5,8 @@ CSRC := pmdfc_amd/csrc
 LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/cceh_engine.hip
-HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h $(CSRC)/packed_image.h include/pmdfc_cceh.h
+SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/cceh_engine.hip $(CSRC)/image_host.hip $(CSRC)/route_host.hip $(CSRC)/filter_host.hip $(CSRC)/trace_host.hip $(CSRC)/extent_host.hip $(CSRC)/dist_host.hip
+HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h $(CSRC)/packed_image.h $(CSRC)/host_common.h $(CSRC)/engine_state.h $(CSRC)/route_host.h include/pmdfc_cceh.h
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
 HOSTLIB := $(LIBDIR)/libpmdfc_gpucceh.so

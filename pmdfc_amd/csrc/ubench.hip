@@ -5,6 +5,7 @@
 // index first goes through a u32 table (like the CCEH directory).
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "host_common.h"
 
 namespace pmdfc {
 
@@ -121,3 +122,34 @@ int launch_scatter16(void* buf, uint64_t nbytes, uint32_t depth, uint64_t nops, 
 }
 
 }  // namespace pmdfc
+
+// ---- the C-ABI wrappers (include/pmdfc_cceh.h): host functions only
+
+using namespace pmdfc;
+
+int pmdfc_ubench_gather64(const void* buf, uint64_t nlines, const uint32_t* table, uint32_t tmask,
+                          uint64_t n_ops, uint64_t seed, uint64_t* out, void* stream) {
+  if (!buf || !out || nlines == 0) return fail(PMDFC_ERR_ARG, "bad argument");
+  launch_gather64(buf, nlines, table, tmask, n_ops, seed, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
+
+int pmdfc_ubench_gather(const void* buf, uint64_t nbytes, uint32_t line, uint32_t depth, const uint32_t* table,
+                        uint32_t tmask, uint64_t n_ops, uint64_t seed, uint64_t* out, uint64_t omask, void* stream) {
+  if (!buf || !out || (omask & (omask + 1))) return fail(PMDFC_ERR_ARG, "bad argument (omask + 1: a power of two)");
+  if (n_ops % depth) return fail(PMDFC_ERR_ARG, "n_ops must be a multiple of depth");
+  if (launch_gather(buf, nbytes, line, depth, table, tmask, n_ops, seed, out, omask, (hipStream_t)stream))
+    return fail(PMDFC_ERR_ARG, "line 64|128, depth 1|2|4, nbytes >= line");
+  HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
+
+int pmdfc_ubench_scatter16(void* buf, uint64_t nbytes, uint32_t depth, uint64_t n_ops, uint64_t seed,
+                           void* stream) {
+  if (!buf) return fail(PMDFC_ERR_ARG, "bad argument");
+  if (launch_scatter16(buf, nbytes, depth, n_ops, seed, (hipStream_t)stream))
+    return fail(PMDFC_ERR_ARG, "depth 1|4, n_ops a multiple of depth, nbytes >= 16");
+  HIPCHK(hipGetLastError());
+  return PMDFC_OK;
+}
