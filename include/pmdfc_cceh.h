@@ -84,10 +84,16 @@ extern "C" {
 #define PMDFC_ST_SPLIT_LOST 10    /* mixed batch: a Get whose key a split of the same batch dropped
                                      (CCEH_hybrid.cpp:24-27) and whose drop could not be placed in
                                      the batch order: only when more than 2^18 entries are dropped
-                                     in one batch (the device drop log overflowed).  Otherwise the
-                                     engine returns the reference's answer (value if the Get
-                                     precedes the insert whose split dropped the key, else MISS).
-                                     error_flags bit 16 is set when it occurs. */
+                                     in one batch (the device drop log overflowed), or when more
+                                     than 64 drops of that one key are logged before the Get (its
+                                     copies re-inserted and dropped again).  No other Get of such a
+                                     batch gets it: a key none of whose copies was dropped keeps
+                                     the reference's answer, and so does every Insert.  Up to 2^18
+                                     drops the engine returns the reference's answer (value if the
+                                     Get precedes the insert whose split dropped the key, else
+                                     MISS).  error_flags bit 16 is set when it occurs, and stays
+                                     set until pmdfc_cceh_reset or pmdfc_cceh_restore; the log starts empty with
+                                     every batch. */
 #define PMDFC_ST_UPDATED 11       /* Insert in upsert mode (PMDFC_CFG_UPSERT): the key was already
                                      in its window; its value was overwritten in place */
 #define PMDFC_ST_ERASED 12        /* Erase: one or more copies of the key were removed */

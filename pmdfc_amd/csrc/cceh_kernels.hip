@@ -709,15 +709,61 @@ void launch_upsert_probe(const uint64_t* keys, uint32_t kvs, const uint8_t* ops,
 // sees the first copy: the pre-batch value while the count never reached 0,
 // else the value of the insert that refilled it, or a miss.  (More than 64
 // such drops of one key before one Get: PMDFC_ST_SPLIT_LOST, error bit 16.)
+//   An overflowed log places no drop, but it takes none to see that no copy
+// of the key was dropped at all: the batch only adds copies, every copy of a
+// key lies in its window, so the window (seg: the key's segment after the
+// batch) then holds the pre-batch copy and one more for each stored insert of
+// the key anywhere in the batch.  The pre-batch copy is still the first one
+// and the early hit stands.  Fewer copies: one of this key's was dropped, at a
+// position the log lost -- PMDFC_ST_SPLIT_LOST.  (A key that is present is not
+// enough: its pre-batch copy may have been dropped before the Get and an
+// insert after the Get may have stored the key again.)
 // (A real call: it takes the fields it reads, not the MixedArgs, which would
 // have to be spilled to scratch to be passed by reference.)
+__device__ __noinline__ bool kept_every_copy(const uint8_t* __restrict__ ops, const uint64_t* __restrict__ keys,
+                                             const uint8_t* __restrict__ st, uint64_t n, uint64_t key,
+                                             const ulonglong2* __restrict__ seg) {
+  const uint32_t lane = __lane_id() & 63u;
+  // the window does not wrap (early 3): slots 4 * line .. + 31, one per lane
+  const uint64_t at = lane < kWindow ? seg[(uint32_t)(hash64(key) & 0xFF) * 4u + lane].x : kInvalid;
+  const uint32_t copies = (uint32_t)__popcll(__ballot(at == key));
+  if (copies == 0) return false;
+  uint32_t stored = 0;  // the batch's stored inserts of the key, 256 ops per step
+  for (uint64_t p0 = 0; p0 < n; p0 += 256) {
+    bool ins[4];
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t p = p0 + 64u * (uint32_t)u + lane;
+      ins[u] = p < n && ops[p] == 1;
+      any |= ins[u];
+    }
+    if (!__ballot(any)) continue;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t p = p0 + 64u * (uint32_t)u + lane;
+      stored += (uint32_t)__popcll(__ballot(ins[u] && keys[p] == key && st[p] == 2));
+    }
+  }
+  return copies == 1u + stored;
+}
+
 __device__ __noinline__ void replay_unchecked_hit(const uint8_t* __restrict__ ops, const uint64_t* __restrict__ keys,
                                                   const uint64_t* __restrict__ vin, uint8_t* __restrict__ st,
-                                                  uint64_t* __restrict__ vout, uint64_t o, DevCtl* __restrict__ ctl,
-                                                  const ulonglong2* __restrict__ drops) {
+                                                  uint64_t* __restrict__ vout, uint64_t o, uint64_t n,
+                                                  DevCtl* __restrict__ ctl, const ulonglong2* __restrict__ drops,
+                                                  const ulonglong2* __restrict__ seg) {
   const uint32_t lane = __lane_id() & 63u;
   const uint64_t key = keys[o];
   const uint32_t nd = ctl->drop_n, nl = min(nd, kDropLog);
+  if (nd > kDropLog) {  // (wave-uniform) the log is incomplete: no drop can be placed
+    if (!kept_every_copy(ops, keys, st, n, key, seg) && lane == 0) {
+      st[o] = 10;  // PMDFC_ST_SPLIT_LOST
+      vout[o] = 0;
+      atomicOr(&ctl->err, 1u << 16);
+    }
+    return;
+  }
   // this key's drops before o, one per lane (at most 64)
   uint32_t dtrig = 0xFFFFFFFFu, cnt = 0;
   for (uint32_t j0 = 0; j0 < nl; j0 += 64) {
@@ -732,8 +778,8 @@ __device__ __noinline__ void replay_unchecked_hit(const uint8_t* __restrict__ op
     }
     cnt += (uint32_t)__popcll(mm);
   }
-  if (cnt == 0 && nd <= kDropLog) return;  // the pre-batch copy outlived the Get: the early hit stands
-  if (nd > kDropLog || cnt > 64u) {        // unplaced
+  if (cnt == 0) return;  // the pre-batch copy outlived the Get: the early hit stands
+  if (cnt > 64u) {       // unplaced
     if (lane == 0) {
       st[o] = 10;  // PMDFC_ST_SPLIT_LOST
       vout[o] = 0;
@@ -816,8 +862,12 @@ __global__ __launch_bounds__(256) void k_mixed_verify(const MixedArgs a) {
   }
   uint64_t m = __ballot(hit);
   if ((!m && !m3) || loss_now == loss_was) return;
-  for (uint64_t b = m3; b; b &= b - 1)
-    replay_unchecked_hit(a.ops, a.keys, a.vin, a.st, a.vout, shfl64(op, __builtin_ctzll(b)), a.ctl, a.drops);
+  for (uint64_t b = m3; b; b &= b - 1) {
+    const uint64_t o = shfl64(op, __builtin_ctzll(b));
+    const ulonglong2* seg = nullptr;  // the key's segment: read only behind an overflowed log
+    if (nd > kDropLog) seg = a.pairs + (size_t)de_seg(dir_entry(bucketed(a.g), hash64(a.keys[o]))) * kSlots;
+    replay_unchecked_hit(a.ops, a.keys, a.vin, a.st, a.vout, o, a.n, a.ctl, a.drops, seg);
+  }
   const uint32_t q = lane & 3u;
   while (m) {
     const int src = __builtin_ctzll(m);

@@ -205,6 +205,40 @@ def _wrap_drop_both_image():
     return [(255, 1, 4), (248, 0, 28), (250, 0, 8), (255, 1, 20)] + [(h, 1, 4) for h in range(6)]
 
 
+_BALLAST_LINES = range(100, 107)
+
+
+def _dense_drop_image(k=7):
+    """N(k), the densest drop of a non-wrapping window: a split that costs
+    33 + 4k inserts and drops 4k entries.  Insert order and slots:
+      32 keys of line 248, child 0 -> 992..1023 (the window is full);
+      4 keys each of lines 256-k .. 255, child 0 -> their windows are full up
+      to slot 1023: they wrap to 0..4k-1.
+    The trigger is a key of line 248 with child bit 1 (it lands in the empty
+    child: no second split).  The split replays the head [0, 4k) first; its
+    entries take 4k slots of [996, 1024), so line 248's 32 entries find
+    32 - 4k free slots in [992, 1024): the last 4k of them are dropped, and
+    nothing else is.  The unit is 32 + 4k slots wide.
+      Ballast: 4 keys each of lines 100..106, child 0 -> 400..427, a cluster
+    of its own that the sweep moves as it lies.  It takes no part in the
+    drops (drop_log_stream leaves it out); it makes the stream longer than
+    256 ops from its first Get on, which the batch cuts of the tests rely on
+    (SPLIT_SHAPE_ABSENT)."""
+    return [(248, 0, 32)] + _per_line(range(256 - k, 256), 0) + _per_line(_BALLAST_LINES, 0)
+
+
+def _dense_drop_wrap_image():
+    """W, dropped entries of a WRAPPING window:
+      32 keys of line 252, child 0 -> 1008..1023 and 0..15;
+      4 keys each of lines 253, 254, 255, child 0 -> 16..19, 20..23, 24..27.
+    The trigger is a key of line 252 with child bit 1.  The split replays the
+    head [0, 28) first: line 252's 16 wrapped entries take 1008..1023, lines
+    253..255 then take 0..11, so the tail's 16 entries of line 252 find 4 free
+    slots (12..15) in their window: 12 are dropped.  44 slots wide.  Ballast
+    as in _dense_drop_image."""
+    return [(252, 0, 32)] + _per_line(range(253, 256), 0) + _per_line(_BALLAST_LINES, 0)
+
+
 _WRAP_LINES = list(range(201, 256)) + list(range(0, 41))
 _WRAP_DROP_LINES = list(range(217, 256)) + list(range(0, 30))
 SPLIT_SHAPES = {
@@ -230,6 +264,10 @@ SPLIT_SHAPES = {
     "cyclic_heads": dict(image=_cyclic_heads_image(), trigger=(245, 0), occupied=97,
                          clusters=[(16, 3), (24, 2), (28, 8), (400, 28), (980, 56)]),
     "wrap_drop_both": dict(image=_wrap_drop_both_image(), trigger=(248, 0), occupied=84, clusters=[(992, 84)]),
+    # the densest drops, 28 and 12 per split: the images drop_log_stream replicates (see the image builders)
+    "dense_drop": dict(image=_dense_drop_image(), trigger=(248, 1), occupied=88, clusters=[(400, 28), (992, 60)]),
+    "dense_drop_wrap": dict(image=_dense_drop_wrap_image(), trigger=(252, 1), occupied=72,
+                            clusters=[(400, 28), (1008, 44)]),
 }
 # name suffix -> (init_cap, hash prefix of the target segment, its local depth):
 # CCEH_hybrid(2)'s segment 0 (child bit = hash bit 62), and segment 0b1011 of
@@ -714,6 +752,129 @@ def keys_from_hash_fields(prefix, pbits, line, count, first=0, below=None):
     h = (np.uint64(prefix) << np.uint64(64 - pbits)) if pbits else np.uint64(0)
     h = h | (n << np.uint64(shift)) | np.uint64(line)
     return unhash64(h)
+
+
+def _field_keys(prefix, pbits, line, number):
+    """keys_from_hash_fields for arrays that broadcast: the key whose hash has
+    `prefix` in its top `pbits` bits, `number` from bit 8 up and home line `line`."""
+    u = np.uint64
+    h = (np.asarray(prefix, u) << u(64 - pbits)) | (np.asarray(number, u) << u(8)) | np.asarray(line, u)
+    return unhash64(h)
+
+
+# A mixed batch whose splits drop a chosen number of entries, up to and past
+# the engine's drop log (2^18 entries: DESIGN §2, PMDFC_ST_SPLIT_LOST).  The
+# segments are copies of the split shapes dense_drop (N(7), 28 drops in 61
+# inserts, the victims in a non-wrapping window), dense_drop_wrap (W, 12 drops,
+# the victims in a wrapping window) and one N(k) that lands on the target.
+DROP_LOG_CAP = 1 << 18
+DL_INSERT, DL_VICTIM, DL_HEAD, DL_BY_LOW, DL_BY_WRAP, DL_TRIGGER, DL_ABSENT = range(7)
+DL_CLASS_NAMES = ["insert", "victim", "head", "bystander_low", "bystander_wrap", "trigger", "absent"]
+_DL_BY_LINES = (100, 251)  # a bystander segment's stored keys: a window that does not wrap, one that does
+
+
+def drop_log_stream(target_drops, depth=14, seed=1, gets_per_segment=4, spare=0):
+    """A table image and one mixed batch on it whose splits drop exactly
+    `target_drops` entries (a multiple of 4), on a depth-`depth` table.
+
+    A random subset of the 2^depth initial segments splits, each once:
+    min(1000, target // 40) W segments (12 drops each), then N(7) segments (28
+    each) and, where a rest r remains, one N(r / 4).  Every key of a splitting
+    segment has child bit 0 but its trigger, a key of the victims' line with
+    child bit 1 (the empty child takes it: no second split).  `spare` further
+    N(7) segments are stored and kept back for a later batch; every other
+    segment is a bystander that holds 4 keys each of lines 100 and 251, of both
+    children, and never splits.  No key is inserted twice, so the entries a
+    batch dropped are the stored inserts that the final table does not hold.
+
+    Returns a dict:
+      depth, target
+      image         (ops, keys, values): inserts only; no split, no loss
+      batch         (ops, keys, values): a round of Gets, every trigger as an
+                    Insert, the same Gets again in another order.  The Gets:
+                    `gets_per_segment` victims of every splitting segment
+                    (line 248 / 252, drawn at random: dropped ones and
+                    survivors), all its head keys (lines 249..255), every
+                    bystander key, the trigger keys (a miss before, a hit
+                    after) and 3 (bystanders: 2) absent keys per segment
+      batch_class   per op of the batch, DL_*
+      after         (ops, keys, values): the same for the spare segments alone,
+                    with every victim and the keys of 32 bystander segments
+      classes       name -> keys: victims (all of them), heads, bystander_low,
+                    bystander_wrap, triggers, absent, spare_victims, spare_triggers"""
+    assert target_drops > 0 and target_drops % 4 == 0
+    u = np.uint64
+    rng = np.random.default_rng(seed)
+    n_w = min(1000, target_drops // 40)
+    n_7, r = divmod(target_drops - 12 * n_w, 28)
+    nseg = 1 << depth
+    n_split = n_w + n_7 + (1 if r else 0)
+    assert n_split + spare + 32 <= nseg, "target too large for the table"
+    order = rng.permutation(nseg).astype(u)
+    pb = depth + 1
+    base = u(int(rng.integers(0, 1 << 20)) << 6)  # the keys of a (segment, child, line) cell: base + 0, 1, ...
+    val_salt = 0xD109
+
+    def splitting(prefixes, vline, hlines):
+        """Per segment (a row each): victims, heads, trigger, absent keys."""
+        p0 = (prefixes << u(1))[:, None]
+        vict = _field_keys(p0, pb, vline, base + np.arange(32, dtype=u)[None, :])
+        hl = np.repeat(np.asarray(list(hlines), u), 4)[None, :]
+        heads = _field_keys(p0, pb, hl, base + np.tile(np.arange(4, dtype=u), hl.size // 4)[None, :])
+        trig = _field_keys(p0 | u(1), pb, vline, base)[:, 0]
+        absent = np.concatenate([_field_keys(p0, pb, vline, base + u(40)), _field_keys(p0 | u(1), pb, vline, base + u(40)),
+                                 _field_keys(p0, pb, 100, base + u(40))], axis=1)
+        return vict, heads, trig, absent
+
+    groups, a = [], 0
+    for n, vline, hlines in ((n_w, 252, range(253, 256)), (n_7, 248, range(249, 256)),
+                             (1 if r else 0, 248, range(256 - r // 4, 256)), (spare, 248, range(249, 256))):
+        groups.append(splitting(order[a:a + n], vline, hlines))
+        a += n
+    by = order[a:]
+    child = np.array([0, 1, 0, 1], u)[None, :]
+    num = base + np.arange(4, dtype=u)[None, :]
+    by_low = _field_keys((by << u(1))[:, None] | child, pb, _DL_BY_LINES[0], num)
+    by_wrap = _field_keys((by << u(1))[:, None] | child, pb, _DL_BY_LINES[1], num)
+    by_absent = np.concatenate([_field_keys((by << u(1))[:, None], pb, ln, base + u(40)) for ln in _DL_BY_LINES], axis=1)
+
+    def stream(parts):
+        """[(op, class, keys)] -> (ops, keys, values), per-op classes."""
+        keys = np.concatenate([k.ravel() for _, _, k in parts])
+        ops = np.concatenate([np.full(k.size, o, np.uint8) for o, _, k in parts])
+        cls = np.concatenate([np.full(k.size, c, np.uint8) for _, c, k in parts])
+        vals = np.where(ops == OP_INSERT, _vals(keys, val_salt), u(0)).astype(u)
+        return (ops, keys, vals), cls
+
+    # the image: each segment's victims, then its heads in line order
+    image, _ = stream([(OP_INSERT, DL_INSERT, np.concatenate([g[0], g[1]], axis=1)) for g in groups]
+                      + [(OP_INSERT, DL_INSERT, np.concatenate([by_low, by_wrap], axis=1))])
+
+    def rounds(gs, sample, bys):
+        """Gets, the triggers, the Gets again."""
+        gets = []
+        for vict, heads, trig, absent in gs:
+            pick = np.argsort(rng.random(vict.shape), axis=1)[:, :sample]
+            gets += [(DL_VICTIM, np.take_along_axis(vict, pick, axis=1)), (DL_HEAD, heads), (DL_TRIGGER, trig),
+                     (DL_ABSENT, absent)]
+        gets += [(DL_BY_LOW, bys[0]), (DL_BY_WRAP, bys[1]), (DL_ABSENT, bys[2])]
+        gk = np.concatenate([k.ravel() for _, k in gets])
+        gc = np.concatenate([np.full(k.size, c, np.uint8) for c, k in gets])
+        p1, p2 = rng.permutation(gk.size), rng.permutation(gk.size)
+        (ops, keys, vals), cls = stream([(OP_GET, 0, gk[p1]), (OP_INSERT, DL_INSERT, np.concatenate([g[2] for g in gs])),
+                                         (OP_GET, 0, gk[p2])])
+        cls[:gk.size] = gc[p1]
+        cls[cls.size - gk.size:] = gc[p2]
+        return (ops, keys, vals), cls
+
+    batch, batch_class = rounds(groups[:3], gets_per_segment, (by_low, by_wrap, by_absent))
+    after, _ = rounds(groups[3:], 32, (by_low[:32], by_wrap[:32], by_absent[:32]))
+    cat = lambda i: np.concatenate([g[i].ravel() for g in groups[:3]])  # noqa: E731
+    classes = dict(victims=cat(0), heads=cat(1), triggers=cat(2),
+                   absent=np.concatenate([cat(3), by_absent.ravel()]), bystander_low=by_low.ravel(),
+                   bystander_wrap=by_wrap.ravel(), spare_victims=groups[3][0].ravel(), spare_triggers=groups[3][2])
+    return dict(depth=depth, target=target_drops, image=image, batch=batch, batch_class=batch_class, after=after,
+                classes=classes)
 
 
 # Streams that run a table out of room (tests/test_gpu_limits.py; the model of

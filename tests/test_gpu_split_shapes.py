@@ -51,7 +51,10 @@ from pmdfc_amd.kv import KV  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = [b + s for s in S.SPLIT_SHAPE_TABLES for b in S.SPLIT_SHAPES]
-GENERIC = ("full_", "wide_wrap")  # kSsPath 2: the generic replay; every other shape 1: the cluster path
+GENERIC = ("full_", "wide_wrap")  # kSsPath 2: the generic replay (a full parent, a wrap unit wider than 128 slots)
+# kSsPath 1: the cluster path (split_team's `fast`: the parent is not full and no unit outgrew the 128-bit
+# window) -- dense_drop's wrap unit is 60 slots wide, dense_drop_wrap's 44
+CLUSTER = ("backlog_", "cyclic_heads", "wrap_drop_both", "dense_drop")
 kSsPath = 6
 
 
@@ -294,6 +297,7 @@ def test_k_split_takes_the_designed_replay(name, shapes, golden, serial, monkeyp
     assert _kernel(_classes(t), 301) == "general"
     assert st[0] == P.ST_INSERTED and np.all(st[1:] == P.ST_MISS)
     rows = t.debug_stamps(4096)[2]
+    assert name.startswith(GENERIC) != name.startswith(CLUSTER)  # every shape says which replay it is designed for
     want = 2 if name.startswith(GENERIC) else 1
     assert int(rows[0, kSsPath]) == want, (name, rows[:2])
     assert not rows[1:, kSsPath].any()  # the only split of its round
