@@ -5,8 +5,7 @@ CSRC := pmdfc_amd/csrc
 LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/cceh_engine.hip $(CSRC)/image_host.hip $(CSRC)/route_host.hip $(CSRC)/filter_host.hip $(CSRC)/trace_host.hip $(CSRC)/extent_host.hip $(CSRC)/dist_host.hip
-HDRS := $(CSRC)/cceh_device.h $(CSRC)/cceh_kernels.h $(CSRC)/knobs.h $(CSRC)/image.h $(CSRC)/packed_image.h $(CSRC)/host_common.h $(CSRC)/engine_state.h $(CSRC)/route_host.h include/pmdfc_cceh.h
+SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/part.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/cceh_engine.hip $(CSRC)/image_host.hip $(CSRC)/route_host.hip $(CSRC)/filter_host.hip $(CSRC)/trace_host.hip $(CSRC)/extent_host.hip $(CSRC)/dist_host.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
 HOSTLIB := $(LIBDIR)/libpmdfc_gpucceh.so
@@ -20,9 +19,12 @@ ERASEKVTEST := $(LIBDIR)/test_gpu_erase_kv
 
 all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(ERASEKVTEST) $(FRONTBENCH) oracle
 
-$(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS)
+# (the compiler writes each object's header dependencies beside it: obj/%.d)
+$(LIBDIR)/obj/%.o: $(CSRC)/%.hip
 	@mkdir -p $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
+
+-include $(OBJS:.o=.d)
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lrccl

@@ -3,9 +3,9 @@
 //
 // The engine owns its HBM (segment arena, occupancy bitmaps, local depths,
 // bucketed directory, batch workspaces) and drives the kernels of
-// cceh_kernels.hip / bucket.hip.  Every batched entry point only ENQUEUES work
-// on the caller's stream; nothing on the Insert/Get/mixed path reads device
-// state back (bucket.hip has the details of every pass):
+// cceh_kernels.hip / part.hip / bucket.hip.  Every batched entry point only
+// ENQUEUES work on the caller's stream; nothing on the Insert/Get/mixed path
+// reads device state back (bucket.hip has the details of every pass):
 //   Insert : k_part -> k_apply_fast (first pass; requests and reserves its
 //            splits) -> k_split -> k_apply_parked -> k_bucket (final pass)
 //   mixed  : k_mixed_prep -> k_mixed_get -> k_part -> the

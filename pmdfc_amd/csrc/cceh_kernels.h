@@ -215,7 +215,7 @@ void launch_owner(const uint64_t* keys, uint64_t n, uint32_t sbits, uint32_t* ow
 void launch_bounds(const uint32_t* sorted_owner, uint64_t n, uint32_t ngroups, uint64_t* starts,
                    hipStream_t s);
 
-// bucket.hip (insert / mixed path)
+// part.hip, bucket.hip (insert / mixed path)
 constexpr uint32_t kPartTile = 8192;       // ops per partition block (A/B: 4096 32.4 us per 1M, 8192 30.9, 16384 57)
 constexpr uint32_t kMaxPartBlocks = 512;   // => max_batch <= 4M
 constexpr uint32_t kMaxP1 = 14;            // <= 16384 directory buckets
@@ -256,10 +256,11 @@ constexpr uint32_t kSplitGroups = PMDFC_SPLIT_GROUPS;  // k_split grid (waves lo
 #endif
 constexpr uint32_t kRecBufs = PMDFC_RECBUFS;
 
-// The argument structs of bucket.hip's kernels, passed by value.  The engine
-// fills them from the batch's BatchPlan (cceh_engine.hip plan_batch, then
-// fill_part_launch / fill_bucket_launch and the callers that patch a batch
-// kind's fields); the launchers add only the kernel, the grid and the gates.
+// The argument structs of part.hip's and bucket.hip's kernels, passed by
+// value.  The engine fills them from the batch's BatchPlan (cceh_engine.hip
+// plan_batch, then fill_part_launch / fill_bucket_launch and the callers that
+// patch a batch kind's fields); the launchers add only the kernel, the grid
+// and the gates.
 
 // k_part
 struct PartArgs {

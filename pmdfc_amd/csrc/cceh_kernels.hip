@@ -1,7 +1,7 @@
 // cceh_kernels.hip -- hand-written gfx950 kernels of the batched CCEH engine:
 // the Get path (one quad per key), the mixed-batch pre-pass, table init and
-// small utilities.  The Insert path (partition + per-bucket apply/split) is in
-// bucket.hip.
+// small utilities.  The Insert path is in part.hip (the partition) and
+// bucket.hip (per-bucket apply / split).
 //
 // Batch semantics: ops are applied as if run serially in batch
 // order on CCEH_hybrid.  A segment's contents depend only on the subsequence

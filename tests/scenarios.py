@@ -302,7 +302,7 @@ def split_shapes(hash64):
     insert (its window is full: the segment splits), Gets of every image key
     again and of SPLIT_SHAPE_ABSENT absent keys.  No split happens before the trigger.
     SPLIT_SHAPES says what each image is and which branch of split_team
-    (bucket.hip) it pins; every shape comes for both SPLIT_SHAPE_TABLES."""
+    (split_device.h) it pins; every shape comes for both SPLIT_SHAPE_TABLES."""
     s = {}
     for suffix in SPLIT_SHAPE_TABLES:
         for base in SPLIT_SHAPES:

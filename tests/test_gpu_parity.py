@@ -65,7 +65,7 @@ def path(request, monkeypatch):
     """default: the engine's own bucket/chunk geometry; tight: at most 2
     buckets and 61-op chunks, so every scenario crosses many chunk boundaries,
     waits through many split rounds and grows sub-directories by many levels
-    inside one bucket (bucket.hip); its Gets skip the flattened directory
+    inside one bucket (bucket_pass.h); its Gets skip the flattened directory
     beyond 3 bits (the hdr/pool fallback of dir_entry)."""
     if request.param == "tight":
         monkeypatch.setenv("PMDFC_P1MAX", "1")

@@ -1,6 +1,6 @@
 """Crafted split images (scenarios.split_shapes) at every split call site.
 
-split_team (bucket.hip) has four mechanisms the uniform streams of the other
+split_team (split_device.h) has four mechanisms the uniform streams of the other
 files hardly touch: the wrap unit's serial replay, the sweep's catch-up from a
 backlog, the generic replay (a full parent, a wrap unit wider than 128 slots)
 and the drop log.  Each shape here pins one of them (scenarios.SPLIT_SHAPES),
