@@ -60,7 +60,6 @@
 
 #include "apply_fast.h"
 #include "bucket_pass.h"
-#include "knobs.h"
 
 namespace pmdfc {
 
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(64, 2) void k_apply(BucketArgs a) {
   bucket_body<false, MIXED, true>(a, blockIdx.x, S);
 }
 // The mixed first pass on a small grid looping over the buckets: launched
-// when the host expects it gated off (BucketLaunch::mixed_small), so the exit
+// when the host expects it gated off (PlanIn::mixed_small), so the exit
 // of its few waves is cheap; exact on any grid (the loop needs more registers
 // than k_apply's one bucket per wave, hence its own kernel)
 __global__ __launch_bounds__(64, 2) void k_apply_mloop(BucketArgs a) {
@@ -593,10 +592,6 @@ __global__ __launch_bounds__(64, 1) void k_medium(BucketArgs a, const uint32_t* 
 // ---------------------------------------------------------------- split round
 
 constexpr uint32_t kSplitWaves = 4;      // waves per k_split workgroup
-#ifndef PMDFC_SPLIT_GROUPS_RAMP
-#define PMDFC_SPLIT_GROUPS_RAMP 1024
-#endif
-constexpr uint32_t kSplitGroupsRamp = PMDFC_SPLIT_GROUPS_RAMP;  // ... while the table ramps (p1 < p1max)
 
 // One wave per requested split, in shard-major order: split k is request i of
 // bucket w; its child id is the segment counter at the start of the pass + k
@@ -754,95 +749,70 @@ __global__ __launch_bounds__(64, 2) void k_apply_fb(BucketArgs a) {
 }
 
 // ------------------------------------------------------------- launchers
-
-#ifndef PMDFC_PARKED_GRID
-#define PMDFC_PARKED_GRID 3072  // (A/B builds; 3 waves per SIMD since round 6: 2048 13.13-13.15 Gops/s against 13.22; 1024 12.25-12.30 in round 4)
-#endif
-#ifndef PMDFC_FINAL_GRID
-#define PMDFC_FINAL_GRID 256  // (A/B builds; 1024 as above)
-#endif
-constexpr uint32_t kParkedGrid = PMDFC_PARKED_GRID;  // k_apply_parked waves (loop over the worklist)
-constexpr uint32_t kFinalGrid = PMDFC_FINAL_GRID;    // k_bucket waves
-#ifndef PMDFC_MIXED_SMALL_GRID
-#define PMDFC_MIXED_SMALL_GRID 256  // (A/B builds) the mixed passes' grid when the host expects them gated off
-#endif
-constexpr uint32_t kMixedSmallGrid = PMDFC_MIXED_SMALL_GRID;
-#ifndef PMDFC_PARKED_GRID_RAMP
-#define PMDFC_PARKED_GRID_RAMP 4096
-#endif
-#ifndef PMDFC_FINAL_GRID_RAMP
-#define PMDFC_FINAL_GRID_RAMP 1024
-#endif
-constexpr uint32_t kParkedGridRamp = PMDFC_PARKED_GRID_RAMP;  // while the table ramps (p1 < p1max)
-constexpr uint32_t kFinalGridRamp = PMDFC_FINAL_GRID_RAMP;
-
-void launch_apply(const BucketLaunch& L, uint32_t mode, hipStream_t s) {
-  if (!L.a.n) return;
-  const bool fast = process_knobs().fast_apply;
+// The batch's LaunchPlan (launch_plan.h) names each pass's kernel, gate and
+// grid; a launcher adds the kernel's workgroup size and the pass's mode.
+static BucketArgs pass_args(const BucketLaunch& L, uint32_t mode, uint32_t gate) {
   BucketArgs a = L.a;
   a.mode = mode;
-  const dim3 g(1u << a.p1);
-  // a gated mixed batch launches the insert-only variant (taken when
-  // k_mixed_get answered every Get) and then the mixed one
-  const bool gated = a.mixed && a.gate_tag != 0;
-  BucketArgs ar = a;
-  if (gated) {
-    ar.gate = 2;
-    a.gate = 1;
+  a.gate = gate;
+  return a;
+}
+
+void launch_first(const BucketLaunch& L, hipStream_t s) {
+  if (!L.a.n) return;
+  const LaunchPlan& p = L.plan;
+  const BucketArgs ar = pass_args(L, 0, p.first_gate), am = pass_args(L, 0, p.mixed_gate);
+  const dim3 g(p.first_grid), gm(p.mixed_grid), b(64);
+  switch (p.first) {
+    case FirstPass::kNone: break;
+    case FirstPass::kFastCp: hipLaunchKernelGGL(k_apply_fast_cp, g, dim3(64 * kCpWaves), 0, s, ar); break;
+    case FirstPass::kWide: hipLaunchKernelGGL(k_apply_wide, g, b, 0, s, ar); break;
+    case FirstPass::kFast: hipLaunchKernelGGL(k_apply_fast, g, b, p.first_lds, s, ar); break;
+    case FirstPass::kFastUps: hipLaunchKernelGGL(k_apply_fast_ups<false>, g, b, 0, s, ar); break;
+    case FirstPass::kFastUpsWide: hipLaunchKernelGGL(k_apply_fast_ups<true>, g, b, 0, s, ar); break;
+    case FirstPass::kGeneral: hipLaunchKernelGGL(k_apply<false>, g, b, 0, s, ar); break;
   }
-  if (mode == 0) {
-    if (gated || !a.mixed) {
-      if (a.upsert && !a.mixed && fast) {
-        // last-writer-wins, insert-only: the lean pass probes each window
-        if (L.wide) hipLaunchKernelGGL(k_apply_fast_ups<true>, g, dim3(64), 0, s, ar);
-        else hipLaunchKernelGGL(k_apply_fast_ups<false>, g, dim3(64), 0, s, ar);
-      } else if (!a.upsert && fast) {
-        // the lean first pass (launch_apply_fallback: the general one over
-        // the buckets it left), its wide variant for large tables
-        if (L.cp) hipLaunchKernelGGL(k_apply_fast_cp, dim3(1u << (a.p1 - kCpSbb)), dim3(64 * kCpWaves), 0, s, ar);
-        else if (L.wide) hipLaunchKernelGGL(k_apply_wide, g, dim3(64), 0, s, ar);
-        else hipLaunchKernelGGL(k_apply_fast, g, dim3(64), process_knobs().fast_lds_pad, s, ar);
-      } else {
-        hipLaunchKernelGGL(k_apply<false>, g, dim3(64), 0, s, ar);
-      }
-    }
-    if (a.mixed && gated && L.mixed_small)
-      hipLaunchKernelGGL(k_apply_mloop, dim3(std::min(1u << a.p1, kMixedSmallGrid)), dim3(64), 0, s, a);
-    else if (a.mixed)
-      hipLaunchKernelGGL(k_apply<true>, g, dim3(64), 0, s, a);
-  } else {
-    // worklist passes: a smaller grid (a ramping table's passes carry more work per batch)
-    const dim3 gw(std::min(1u << a.p1, L.ramp ? kParkedGridRamp : kParkedGrid));
-    if (gated) {  // (both variants as two launches: configs 3 / 4 7.17-7.25 / 6.04-6.06 against 7.31-7.34 / 6.12-6.15)
-      hipLaunchKernelGGL(k_apply_parked_gated, gw, dim3(64), 0, s, ar, a);
-    } else {
-      if (gated || !a.mixed) hipLaunchKernelGGL(k_apply_parked<false>, gw, dim3(64), 0, s, ar);
-      if (a.mixed)
-        hipLaunchKernelGGL(k_apply_parked<true>, gated && L.mixed_small ? dim3(std::min(gw.x, kMixedSmallGrid)) : gw,
-                           dim3(64), 0, s, a);
-    }
+  switch (p.mixed) {
+    case MixedPass::kNone: break;
+    case MixedPass::kApply: hipLaunchKernelGGL(k_apply<true>, gm, b, 0, s, am); break;
+    case MixedPass::kLoop: hipLaunchKernelGGL(k_apply_mloop, gm, b, 0, s, am); break;
   }
 }
 
-void launch_apply_fallback(const BucketLaunch& L, hipStream_t s) {
-  if (!L.a.n || !process_knobs().fast_apply || (L.a.upsert && L.a.mixed)) return;  // (no lean pass was launched)
-  const bool gated = L.a.mixed && L.a.gate_tag != 0;
-  if (L.a.mixed && !gated) return;
-  BucketArgs a = L.a;
-  if (gated) a.gate = 2;  // with the insert-only variant it follows
-  hipLaunchKernelGGL(k_apply_fb, dim3(1u << a.p1), dim3(64), 0, s, a);
+void launch_fallback(const BucketLaunch& L, hipStream_t s) {
+  if (!L.a.n || !L.plan.fb) return;
+  hipLaunchKernelGGL(k_apply_fb, dim3(1u << L.a.p1), dim3(64), 0, s, pass_args(L, 0, L.plan.fb_gate));
+}
+
+void launch_split_round(const BucketLaunch& L, hipStream_t s) {
+  if (!L.a.n) return;
+  hipLaunchKernelGGL(k_split, dim3(L.plan.split_grid), dim3(64 * kSplitWaves), 0, s,
+                     split_args(L.a, L.split_stamps, L.plan.team_max));
+}
+
+void launch_parked(const BucketLaunch& L, hipStream_t s) {
+  if (!L.a.n) return;
+  const dim3 g(L.plan.parked_grid), b(64);
+  switch (L.plan.parked) {
+    case ParkedPass::kInsert: hipLaunchKernelGGL(k_apply_parked<false>, g, b, 0, s, pass_args(L, 2, 0)); break;
+    case ParkedPass::kMixed: hipLaunchKernelGGL(k_apply_parked<true>, g, b, 0, s, pass_args(L, 2, 0)); break;
+    case ParkedPass::kGated:  // (both variants as two launches: configs 3 / 4 7.17-7.25 / 6.04-6.06 against 7.31-7.34 / 6.12-6.15)
+      hipLaunchKernelGGL(k_apply_parked_gated, g, b, 0, s, pass_args(L, 2, 2), pass_args(L, 2, 1));
+      break;
+  }
 }
 
 void launch_final(const BucketLaunch& L, hipStream_t s) {
   if (!L.a.n) return;
-  const dim3 g(std::min(1u << L.a.p1, L.ramp ? kFinalGridRamp : kFinalGrid));
-  if (L.a.mixed) hipLaunchKernelGGL(k_bucket<true>, g, dim3(64), 0, s, L.a);
-  else hipLaunchKernelGGL(k_bucket<false>, g, dim3(64), 0, s, L.a);
+  const dim3 g(L.plan.final_grid), b(64);
+  switch (L.plan.fin) {
+    case FinalPass::kInsert: hipLaunchKernelGGL(k_bucket<false>, g, b, 0, s, L.a); break;
+    case FinalPass::kMixed: hipLaunchKernelGGL(k_bucket<true>, g, b, 0, s, L.a); break;
+  }
 }
 
-void launch_mixed_small(const BucketLaunch& L, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
+void launch_mixed_small(const BucketArgs& a, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                         hipStream_t s) {
-  const BucketArgs& a = L.a;
   if (!a.n) return;
   if (a.n <= 64) {
     hipLaunchKernelGGL(k_mixed_tiny, dim3(1), dim3(64), 0, s, a, ops, keys, vin);
@@ -856,19 +826,12 @@ void launch_serve(const ServeArgs& sa, hipStream_t s) {
   hipLaunchKernelGGL(k_serve, dim3(sa.nwaves), dim3(64), 0, s, sa);
 }
 
-void launch_medium(const BucketLaunch& L, const uint32_t* touched, hipStream_t s) {
-  const BucketArgs& a = L.a;
+void launch_medium(const BucketArgs& a, const uint32_t* touched, hipStream_t s) {
   if (!a.n) return;
   const uint32_t npb = 1u << (a.p1 - a.sbb);
   const dim3 g((uint32_t)std::min<uint64_t>(std::max<uint64_t>(a.n, 64), npb));  // >= the touched buckets
   if (a.mixed) hipLaunchKernelGGL(k_medium<true>, g, dim3(64), 0, s, a, touched);
   else hipLaunchKernelGGL(k_medium<false>, g, dim3(64), 0, s, a, touched);
-}
-
-void launch_split_round(const BucketLaunch& L, hipStream_t s) {
-  if (!L.a.n) return;
-  hipLaunchKernelGGL(k_split, dim3(L.ramp ? kSplitGroupsRamp : kSplitGroups), dim3(64 * kSplitWaves), 0, s,
-                     split_args(L.a, L.split_stamps, process_knobs().split_team_max));
 }
 
 }  // namespace pmdfc

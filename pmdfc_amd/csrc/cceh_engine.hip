@@ -55,6 +55,15 @@ int pmdfc::read_ctl(pmdfc_cceh* t, hipStream_t s) {
   return PMDFC_OK;
 }
 
+// the bounds of the *_batches entry points: non-decreasing, no batch past max_batch
+static int check_bounds(const uint64_t* bounds, uint32_t nbatches, uint64_t max_batch) {
+  for (uint32_t i = 0; i < nbatches; ++i) {
+    if (bounds[i + 1] < bounds[i]) return fail(PMDFC_ERR_ARG, "bounds must be non-decreasing");
+    if (bounds[i + 1] - bounds[i] > max_batch) return fail(PMDFC_ERR_ARG, "a batch exceeds max_batch");
+  }
+  return PMDFC_OK;
+}
+
 // The per-bucket counters (the slots of every bucket geometry so far) and,
 // from them and the control block read_ctl left in hctl, the deepest local
 // depth: stats() sums the rest, dump() needs the depth alone.
@@ -318,12 +327,11 @@ static void fill_record_view(const pmdfc_cceh* t, const BatchPlan& b, Args& a) {
   a.ovf_base = (uint64_t)b.cap << pbits;
 }
 
-// The bucket passes' arguments for the batch of plan b (B{}: the launchers'
-// a.mode / a.gate, the gated mixed batches' gate_tag / mseen / mixed_small and
-// the drop log stay zero unless the caller sets them).
-static void fill_bucket_launch(const pmdfc_cceh* t, const BatchPlan& b, BucketLaunch& L, uint64_t n, uint8_t* st,
-                               uint64_t* vout, bool mixed) {
-  BucketArgs& a = L.a;
+// The bucket kernels' arguments for the batch of plan b (A{}: the launchers'
+// a.mode / a.gate, the gated mixed batches' gate_tag / mseen and the drop log
+// stay zero unless the caller sets them).
+static void fill_bucket_args(const pmdfc_cceh* t, const BatchPlan& b, BucketArgs& a, uint64_t n, uint8_t* st,
+                             uint64_t* vout, bool mixed) {
   a.n = n;
   fill_record_view(t, b, a);
   a.chunk = (t->kn.chunk == 0 || t->kn.chunk > kChunkWave) ? kChunkWave : t->kn.chunk;
@@ -368,19 +376,44 @@ static void fill_bucket_launch(const pmdfc_cceh* t, const BatchPlan& b, BucketLa
   a.fbl = t->fbl;
   a.par = b.par;
   a.hint = t->d_hint;
-  L.wide = b.wide;
-  L.fb = b.fb;
-  L.cp = b.cp;
+}
+
+// The launch plan's inputs but for the hints: the batch's kind (a mixed batch
+// is gated unless the table upserts), the process knobs, the bucket bits.
+static PlanIn plan_in(const pmdfc_cceh* t, bool mixed) {
+  const ProcessKnobs& K = process_knobs();
+  PlanIn in{};
+  in.mixed = mixed;
+  in.upsert = t->upsert != 0;
+  in.gated = mixed && !t->upsert;
+  in.fast_apply = K.fast_apply;
+  in.fast_lds_pad = K.fast_lds_pad;
+  in.split_team_max = K.split_team_max;
+  in.p1 = t->p1;
+  return in;
+}
+
+// A general batch's bucket passes: the kernels' arguments and the launch plan
+// (launch_plan.h), decided here once.  tag: a gated mixed batch's epoch.
+static void fill_bucket_launch(const pmdfc_cceh* t, const BatchPlan& b, BucketLaunch& L, uint64_t n, uint8_t* st,
+                               uint64_t* vout, bool mixed, uint32_t tag = 0, bool mixed_small = false) {
+  fill_bucket_args(t, b, L.a, n, st, vout, mixed);
   L.split_stamps = b.stamps ? b.stamps + stamp_split_off(t) : nullptr;
+  PlanIn in = plan_in(t, mixed);
+  in.wide = b.wide;
+  in.cp = b.cp;
+  in.fb = b.fb;
+  in.mixed_small = mixed_small;
   // the larger grids of the passes after the first while the table ramps,
   // or is still small for the batch (more than 32 ops per segment: windows
   // fill within the batch, the final pass has work): the CCEH_hybrid(2)
   // ramp 5.11 -> 5.75 Gops/s with them after p1max too, config 2 (16 ops per
   // segment at its start) 12.56 against 12.41 without (profiles/r05/grids/)
-  {
-    const uint64_t segs = __atomic_load_n(t->h_hint, __ATOMIC_RELAXED);
-    L.ramp = (t->p1 < t->p1max || n > 32ull * std::max<uint64_t>(segs, 1)) ? 1u : 0u;
-  }
+  const uint64_t segs = __atomic_load_n(t->h_hint, __ATOMIC_RELAXED);
+  in.ramp = t->p1 < t->p1max || n > 32ull * std::max<uint64_t>(segs, 1);
+  L.plan = plan_launches(in);
+  L.a.gate_tag = in.gated ? tag : 0u;
+  if (!L.plan.probe) L.a.upos = nullptr;  // (the first pass reads it only after k_upsert_probe)
 }
 
 // k_part's arguments for the batch of plan b (P{}: the medium batches' init /
@@ -446,32 +479,29 @@ static void fill_part_join(PartArgs& p, const MixedArgs& a) {
   p.tag = a.tag;
 }
 
-// The bucket passes of one insert / mixed batch, all on the stream: a first
-// apply pass, then kSplitRounds x {split round, apply pass over the parked
-// ops (it commits the round's splits first)}, then the final pass for
-// whatever is still parked -- ops whose segment needs a second split in the
-// same batch, rare enough that one pipelined round measured best (an empty
-// round costs ~15 us of launches).
-static constexpr int kSplitRounds = 1;  // (a batch's grant shards hold one round of requests)
-
+// The bucket passes of one insert / mixed batch, all on the stream, as the
+// batch's launch plan names them: a first apply pass, ONE split round (a
+// batch's grant shards hold one round of requests), the apply pass over the
+// parked ops (it commits the round's splits first and requests none), then
+// the final pass for whatever is still parked -- ops whose segment needs a
+// second split in the same batch, rare enough that one pipelined round
+// measured best (an empty round costs ~15 us of launches).
 static void run_bucket_passes(pmdfc_cceh* t, const BucketLaunch& B, hipStream_t s) {
   t->timing.begin(PMDFC_K_PROCESS, s);
-  launch_apply(B, 0, s);
+  launch_first(B, s);
   // the general first pass over the buckets the lean one declined: its own
   // launch (k_apply_fb, requesting splits for the split round) only where
   // declines are expected, a table past the wide pass's 128-entry
   // sub-directories; otherwise the rare declined bucket takes its first pass
   // in k_apply_parked (an empty k_apply_fb launch costs ~3.2 us a batch)
-  if (B.fb) {
+  if (B.plan.fb_class) {
     t->timing.begin(PMDFC_K_FINAL, s);  // (the fallback first pass is timed with the final pass)
-    launch_apply_fallback(B, s);
+    launch_fallback(B, s);
   }
-  for (int r = 0; r < kSplitRounds; ++r) {
-    t->timing.begin(PMDFC_K_SPLIT, s);
-    launch_split_round(B, s);
-    t->timing.begin(PMDFC_K_PARKED, s);
-    launch_apply(B, r + 1 < kSplitRounds ? 1 : 2, s);  // the last one requests nothing
-  }
+  t->timing.begin(PMDFC_K_SPLIT, s);
+  launch_split_round(B, s);
+  t->timing.begin(PMDFC_K_PARKED, s);
+  launch_parked(B, s);
   t->timing.begin(PMDFC_K_FINAL, s);
   launch_final(B, s);
 }
@@ -633,7 +663,10 @@ int pmdfc_cceh_create(const pmdfc_cceh_config_t* cfg, pmdfc_cceh_t** out) {
   if (t->kn.stamps) {
     const uint64_t bytes = t->kn.stamp_rot * stamp_words(t) * sizeof(uint64_t);
     ALLOC(t->stamps, bytes);
-    HIPCHK(hipMemset(t->stamps, 0, bytes));
+    if ((e = hipMemset(t->stamps, 0, bytes)) != hipSuccess) {
+      pmdfc_cceh_destroy(t);
+      return fail(PMDFC_ERR_HIP, "hipMemset(t->stamps, 0, bytes)", e);
+    }
   }
 #undef ALLOC
   {
@@ -748,8 +781,7 @@ int pmdfc_cceh_get(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* vout, uint8_
 int pmdfc_cceh_get_batches(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* vout, uint8_t* st,
                            const uint64_t* bounds, uint32_t nbatches, void* stream) {
   if (!t || !bounds || (nbatches && (!keys || !vout || !st))) return fail(PMDFC_ERR_ARG, "null argument");
-  for (uint32_t i = 0; i < nbatches; ++i)
-    if (bounds[i + 1] < bounds[i]) return fail(PMDFC_ERR_ARG, "bounds must be non-decreasing");
+  if (int rc = check_bounds(bounds, nbatches, ~0ull)) return rc;  // (a Get batch may be any size)
   if (nbatches == 0) return PMDFC_OK;
 #ifdef PMDFC_GETB_PER_BATCH  // (A/B builds: one launch per batch)
   for (uint32_t i = 0; i < nbatches; ++i)
@@ -837,10 +869,10 @@ static int small_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   int rc = rebucket_now(t, s);  // (a table coarser than p1max: one sync, as the general path)
   if (rc) return rc;
   const BatchPlan b = plan_batch(t, false, n, false);  // (no records)
-  BucketLaunch B{};
-  fill_bucket_launch(t, b, B, n, st, vout, true);
+  BucketArgs A{};
+  fill_bucket_args(t, b, A, n, st, vout, true);
   t->timing.begin(PMDFC_K_PROCESS, s);
-  launch_mixed_small(B, ops, keys, vin, s);
+  launch_mixed_small(A, ops, keys, vin, s);
   t->timing.end(s);
   finish_batch(t, b, kPathSmall);
   HIPCHK(hipGetLastError());
@@ -863,11 +895,11 @@ static int medium_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys,
   P.init = ops ? 1u : 0u;
   P.vout = vout;
   P.touched = t->touched;
-  BucketLaunch B{};
-  fill_bucket_launch(t, b, B, n, st, vout, ops != nullptr);
+  BucketArgs A{};
+  fill_bucket_args(t, b, A, n, st, vout, ops != nullptr);
   t->timing.begin(PMDFC_K_PROCESS, s);
   launch_part(P, s);
-  launch_medium(B, t->touched, s);
+  launch_medium(A, t->touched, s);
   t->timing.end(s);
   finish_batch(t, b, kPathMedium);
   HIPCHK(hipGetLastError());
@@ -883,11 +915,7 @@ static int insert_one(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   BucketLaunch B{};
   fill_bucket_launch(t, b, B, n, st, nullptr, false);
   t->timing.begin(PMDFC_K_ROUTE, s);
-  // upsert: the lean first pass probes each window itself; the pre-batch
-  // probe serves the general pass only when the lean one is off
-  const bool probe = t->upsert && !process_knobs().fast_apply;
-  if (probe) launch_upsert_probe(keys, kvs, nullptr, n, t->geo(), t->pairs, t->upos, s);
-  else B.a.upos = nullptr;
+  if (B.plan.probe) launch_upsert_probe(keys, kvs, nullptr, n, t->geo(), t->pairs, t->upos, s);
   launch_part(P, s);
   run_bucket_passes(t, B, s);
   t->timing.end(s);
@@ -964,9 +992,11 @@ int pmdfc::pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   HIPCHK(hipMemsetAsync(t->cursor + p * t->cblk, 0, t->cblk * sizeof(uint32_t), P));
   PartArgs PL{};
   fill_part_launch(t, b, PL, nullptr, keys, vin, kvs, st, n);
+  BucketLaunch B{};
+  fill_bucket_launch(t, b, B, n, st, nullptr, false);
+  B.a.clear_next = 0;  // the next batch's cursors may already be in use
   hipEvent_t e0 = t->timing.span_begin(P);
-  const bool probe = t->upsert && !process_knobs().fast_apply;  // (as insert_one)
-  if (probe) {  // the probe reads the table: after the previous batch (ev_done)
+  if (B.plan.probe) {  // the probe reads the table: after the previous batch (ev_done)
     if (k >= 1) HIPCHK(hipStreamWaitEvent(P, t->ev_done[(p + kRecBufs - 1) % kRecBufs], 0));
     launch_upsert_probe(keys, kvs, nullptr, n, t->geo(), t->pairs, t->upos, P);
   }
@@ -974,10 +1004,6 @@ int pmdfc::pipe_batch(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
   t->timing.span_end(PMDFC_K_ROUTE, e0, P);
   HIPCHK(hipEventRecord(t->ev_part[p], P));
   HIPCHK(hipStreamWaitEvent(s, t->ev_part[p], 0));
-  BucketLaunch B{};
-  fill_bucket_launch(t, b, B, n, st, nullptr, false);
-  B.a.clear_next = 0;  // the next batch's cursors may already be in use
-  if (!probe) B.a.upos = nullptr;
   run_bucket_passes(t, B, s);
   t->timing.end(s);
   HIPCHK(hipEventRecord(t->ev_done[p], s));
@@ -1016,8 +1042,7 @@ static int pipe_group(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin
     BucketLaunch B{};
     fill_bucket_launch(t, plans[j], B, n, st + o, nullptr, false);
     B.a.clear_next = 0;  // the next batch's cursors may already be in use
-    B.a.upos = nullptr;
-    run_bucket_passes(t, B, s);
+    run_bucket_passes(t, B, s);  // (no probe in B.plan: pmdfc_cceh_insert_batches sends those batches one by one)
     t->timing.end(s);
   }
   HIPCHK(hipEventRecord(t->ev_gdone[gi & 1u], s));
@@ -1035,10 +1060,7 @@ int pmdfc::pipe_end(pmdfc_cceh_t* t, hipStream_t s) {
 int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint64_t* vin, uint8_t* st,
                               const uint64_t* bounds, uint32_t nbatches, void* stream) {
   if (!t || !bounds || (nbatches && (!keys || !vin || !st))) return fail(PMDFC_ERR_ARG, "null argument");
-  for (uint32_t i = 0; i < nbatches; ++i) {
-    if (bounds[i + 1] < bounds[i]) return fail(PMDFC_ERR_ARG, "bounds must be non-decreasing");
-    if (bounds[i + 1] - bounds[i] > t->max_batch) return fail(PMDFC_ERR_ARG, "a batch exceeds max_batch");
-  }
+  if (int rc = check_bounds(bounds, nbatches, t->max_batch)) return rc;
   if (nbatches == 0) return PMDFC_OK;
   std::lock_guard<std::mutex> lk(t->mu);
   DevGuard g(t->dev);
@@ -1053,7 +1075,7 @@ int pmdfc_cceh_insert_batches(pmdfc_cceh_t* t, const uint64_t* keys, const uint6
   // the partition stream starts after everything already on the caller's
   // stream (the inputs, and every earlier batch)
   int rc = pipe_begin(t, s);
-  if (t->upsert && !process_knobs().fast_apply) {  // (the upsert probe reads the table: batch by batch)
+  if (plan_launches(plan_in(t, false)).probe) {  // (the upsert probe reads the table: batch by batch)
     uint32_t k = 0;
     for (uint32_t i = i0; i < nbatches && rc == PMDFC_OK; ++i) {
       const uint64_t o = bounds[i], n = bounds[i + 1] - bounds[i];
@@ -1118,22 +1140,18 @@ static int mixed_one(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* keys, 
   fill_part_launch(t, b, P, ops, keys, vin, 1, st, n);
   fill_part_join(P, M);
   P.vout = vout;
-  BucketLaunch B{};
-  fill_bucket_launch(t, b, B, n, st, vout, true);
   // when k_mixed_get answered every Get, the insert-only apply passes run
-  // (upsert batches always take the mixed ones)
-  B.a.gate_tag = M.ups ? 0u : tag;
-  // the mixed passes on small grids unless a mixed batch of the last 64 ran
-  // them (the word may lag the batches in flight: either grid is exact)
+  // (gated by tag; upsert batches always take the mixed ones).  The mixed
+  // first pass on a small grid unless a mixed batch of the last 64 ran it (the
+  // word may lag the batches in flight: either grid is exact) or PMDFC_MIXED_SMALL=0
+  const uint32_t last = __atomic_load_n(t->h_hint + kHintMixed, __ATOMIC_RELAXED);
+  const bool mixed_small = !M.ups && !(last != 0 && tag - last < 64u) && process_knobs().mixed_small;
+  BucketLaunch B{};
+  fill_bucket_launch(t, b, B, n, st, vout, true, tag, mixed_small);
   B.a.mseen = t->d_hint + kHintMixed;
-  {
-    const uint32_t last = __atomic_load_n(t->h_hint + kHintMixed, __ATOMIC_RELAXED);
-    // (PMDFC_MIXED_SMALL=0: always on full grids)
-    B.mixed_small = (last != 0 && tag - last < 64u) || !process_knobs().mixed_small ? 0u : 1u;
-  }
   B.a.drops = M.drops;  // splits log what they drop, for k_mixed_verify
   t->timing.begin(PMDFC_K_ROUTE, s);
-  if (M.ups) launch_upsert_probe(keys, 1, ops, n, M.g, M.pairs, t->upos, s);
+  if (B.plan.probe) launch_upsert_probe(keys, 1, ops, n, M.g, M.pairs, t->upos, s);
   launch_part(P, s);
   run_bucket_passes(t, B, s);
   launch_mixed_verify(M, s);
@@ -1173,10 +1191,7 @@ int pmdfc_cceh_mixed_batches(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t
                              uint64_t* vout, uint8_t* st, const uint64_t* bounds, uint32_t nbatches, void* stream) {
   if (!t || !bounds || (nbatches && (!ops || !keys || !vin || !vout || !st)))
     return fail(PMDFC_ERR_ARG, "null argument");
-  for (uint32_t i = 0; i < nbatches; ++i) {
-    if (bounds[i + 1] < bounds[i]) return fail(PMDFC_ERR_ARG, "bounds must be non-decreasing");
-    if (bounds[i + 1] - bounds[i] > t->max_batch) return fail(PMDFC_ERR_ARG, "a batch exceeds max_batch");
-  }
+  if (int rc = check_bounds(bounds, nbatches, t->max_batch)) return rc;
   for (uint32_t i = 0; i < nbatches; ++i) {
     const uint64_t o = bounds[i], n = bounds[i + 1] - bounds[i];
     if (n == 0) continue;
@@ -1201,10 +1216,8 @@ static int serve_start(pmdfc_cceh_t* t, uint32_t nwaves, pmdfc_serve_req* req, p
   HIPCHK(hipHostGetDevicePointer(&dr, resp, 0));
   HIPCHK(hipHostGetDevicePointer(&dc, ctl, 0));
   const BatchPlan b = plan_batch(t, false, 64, false);  // (no records)
-  BucketLaunch B{};
-  fill_bucket_launch(t, b, B, 64, t->srv_st, t->srv_vout, true);
   ServeArgs V{};
-  V.a = B.a;
+  fill_bucket_args(t, b, V.a, 64, t->srv_st, t->srv_vout, true);
   V.req = (const pmdfc_serve_req*)dq;
   V.resp = (pmdfc_serve_resp*)dr;
   V.ctl = (pmdfc_serve_ctl*)dc;
@@ -1248,27 +1261,20 @@ int pmdfc_cceh_mixed_host(pmdfc_cceh_t* t, const uint8_t* ops, const uint64_t* k
   DevGuard g(t->dev);
   for (uint64_t off = 0; off < n; off += t->max_batch) {
     const uint64_t m = std::min<uint64_t>(t->max_batch, n - off);
-    uint8_t *d_ops = nullptr, *d_st = nullptr;
-    uint64_t *d_keys = nullptr, *d_vin = nullptr, *d_vout = nullptr;
-    HIPCHK(hipMalloc(&d_ops, m));
-    HIPCHK(hipMalloc(&d_st, m));
-    HIPCHK(hipMalloc(&d_keys, m * 8));
-    HIPCHK(hipMalloc(&d_vin, m * 8));
-    HIPCHK(hipMalloc(&d_vout, m * 8));
-    HIPCHK(hipMemcpy(d_ops, ops + off, m, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_keys, keys + off, m * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_vin, vin + off, m * 8, hipMemcpyHostToDevice));
-    int rc = pmdfc_cceh_mixed(t, d_ops, d_keys, d_vin, d_vout, d_st, m, nullptr);
-    if (rc == PMDFC_OK) {
-      HIPCHK(hipMemcpy(vout + off, d_vout, m * 8, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(st + off, d_st, m, hipMemcpyDeviceToHost));
-    }
-    (void)hipFree(d_ops);
-    (void)hipFree(d_st);
-    (void)hipFree(d_keys);
-    (void)hipFree(d_vin);
-    (void)hipFree(d_vout);
-    if (rc) return rc;
+    DevTmp d_ops, d_st, d_keys, d_vin, d_vout;  // (freed at the end of the chunk, on every path)
+    HIPCHK(hipMalloc(&d_ops.p, m));
+    HIPCHK(hipMalloc(&d_st.p, m));
+    HIPCHK(hipMalloc(&d_keys.p, m * 8));
+    HIPCHK(hipMalloc(&d_vin.p, m * 8));
+    HIPCHK(hipMalloc(&d_vout.p, m * 8));
+    HIPCHK(hipMemcpy(d_ops.p, ops + off, m, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_keys.p, keys + off, m * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_vin.p, vin + off, m * 8, hipMemcpyHostToDevice));
+    if (int rc = pmdfc_cceh_mixed(t, (const uint8_t*)d_ops.p, (const uint64_t*)d_keys.p, (const uint64_t*)d_vin.p,
+                                  (uint64_t*)d_vout.p, (uint8_t*)d_st.p, m, nullptr))
+      return rc;
+    HIPCHK(hipMemcpy(vout + off, d_vout.p, m * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st + off, d_st.p, m, hipMemcpyDeviceToHost));
   }
   return PMDFC_OK;
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "cceh_device.h"
+#include "launch_plan.h"
 #include "../../include/pmdfc_cceh.h"
 
 namespace pmdfc {
@@ -220,7 +221,6 @@ constexpr uint32_t kPartTile = 8192;       // ops per partition block (A/B: 4096
 constexpr uint32_t kMaxPartBlocks = 512;   // => max_batch <= 4M
 constexpr uint32_t kMaxP1 = 14;            // <= 16384 directory buckets
 constexpr uint32_t kServeWavesMax = 64;     // serving waves (PMDFC_SERVE_WAVES_MAX)
-constexpr uint32_t kCpSbb = 3;             // coarse partition: 8 directory buckets per partition bucket
 constexpr uint32_t kMaxPartBits = 13;      // <= 8192 partition buckets
 // A partition bucket's record region is cut into kPartSubs sub-regions, one
 // per XCD-sharing class of k_part blocks (blocks b and b + 8 share an XCD,
@@ -243,10 +243,6 @@ constexpr uint32_t kSplitCap = 64;    // split requests per directory bucket and
 // per-bucket cumulative counters: lines, waited, splits, split loss, runs,
 // rounds, {max rounds | max local depth << 16 | growths << 32}, spare
 constexpr int kWStat = 8;
-#ifndef PMDFC_SPLIT_GROUPS
-#define PMDFC_SPLIT_GROUPS 512  // (A/B builds; 1024: two dispatch rounds at 2 waves/SIMD, 12.41-12.44 against 12.56 Gops/s)
-#endif
-constexpr uint32_t kSplitGroups = PMDFC_SPLIT_GROUPS;  // k_split grid (waves loop over the requested splits)
 // partition record buffers (records, cursors, k_part overflow slots):
 // pmdfc_cceh_insert_batches partitions groups of up to kRecBufs / 2 batches
 // ahead (pipe_group); the per-batch pipeline of the routed loop (pipe_batch)
@@ -258,9 +254,9 @@ constexpr uint32_t kRecBufs = PMDFC_RECBUFS;
 
 // The argument structs of part.hip's and bucket.hip's kernels, passed by
 // value.  The engine fills them from the batch's BatchPlan (cceh_engine.hip
-// plan_batch, then fill_part_launch / fill_bucket_launch and the callers that
-// patch a batch kind's fields); the launchers add only the kernel, the grid
-// and the gates.
+// plan_batch, then fill_part_launch / fill_bucket_args and the callers that
+// patch a batch kind's fields); the launchers add only what the batch's
+// LaunchPlan (launch_plan.h) names: the kernel, the grid, mode and gate.
 
 // k_part
 struct PartArgs {
@@ -353,50 +349,45 @@ struct BucketArgs {
   uint32_t* fbl;         // [2^p1max] per bucket: bit 0 k_apply_fast declined it (-> k_apply_fb), bits 1+ declines so far
   uint32_t* hint;        // device-mapped pinned word: k_apply_parked leaves the segment count after
                          // this batch's grants there (host hint)
-  uint32_t mode;         // (launcher) k_apply: 0 first pass, 1 parked-op pass, 2 parked-op pass without
-                         // split requests (the last before the final pass)
+  uint32_t mode;         // (launcher) 0 first pass; 2 parked-op pass without split requests, the one
+                         // the host sends (the kernels also take 1: a parked-op pass that requests)
   // worklists: the passes after k_apply visit only the buckets that have work
   uint32_t* fin;         // [2][2^p1] by batch parity: k_bucket's worklist (count: ctl->nfin[par])
   uint32_t par;          // this batch's parity
-  // mixed batches: both apply variants are launched and exactly one runs.
-  // gate 1 (MIXED kernels) runs iff ctl->pget == gate_tag (k_mixed_get left
-  // a Get pending), gate 2 (the insert-only kernels) iff not; 0: always.
-  // gate: (launcher); gate_tag: != 0 for a gated mixed batch
+  // gated mixed batches: both apply variants are launched and exactly one
+  // runs.  gate 1 (MIXED kernels) runs iff ctl->pget == gate_tag (k_mixed_get
+  // left a Get pending), gate 2 (the insert-only kernels) iff not; 0: always.
+  // gate: (launcher, from the LaunchPlan); gate_tag: != 0 for a gated batch
   uint32_t gate, gate_tag;
-  uint32_t* mseen;       // host-mapped: k_apply<true> stores gate_tag when it runs (BucketLaunch::mixed_small)
+  uint32_t* mseen;       // host-mapped: k_apply<true> stores gate_tag when it runs (PlanIn::mixed_small)
 };
-// what the host-side launch decisions read and the kernels do not
+// A general batch's bucket passes: the arguments and the launches they go to
 struct BucketLaunch {
   BucketArgs a;
-  uint32_t wide;     // the lean first pass in its wide variant (k_apply_wide: sub-directories up to 128 entries)
-  uint32_t fb;       // launch k_apply_fb after it (else k_apply_parked takes the declined buckets)
-  uint32_t cp;       // coarse partition (sbb == 3): the lean first pass is k_apply_fast_cp
-  uint32_t ramp;     // the table still ramps (p1 < p1max) or is small for the batch: the larger grids
-  // gated mixed batches: the host expects the mixed passes to stay gated off
-  // (no recent batch ran them, a.mseen) and launches them on small looping
-  // grids, so their exit costs less
-  uint32_t mixed_small;
+  LaunchPlan plan;
   uint64_t* split_stamps;  // debug: 8 stamps for each of the first kSplitStamps splits, or null
 };
-// k_apply: mode 0 = first pass over the batch's records, 1 = pass over the
-// parked ops (after a split round); final: k_bucket (inline splits, the rest)
-void launch_apply(const BucketLaunch& L, uint32_t mode, hipStream_t s);
-// k_apply_fb after the lean first pass (insert-only batches; nothing otherwise)
-void launch_apply_fallback(const BucketLaunch& L, hipStream_t s);
+// The passes in order, each a switch over L.plan (nothing for an empty batch):
+// the first pass over the batch's records (mode 0), insert-only and mixed
+// variant; k_apply_fb where the plan has it follow a lean first pass; after
+// the split round the pass over the parked ops (mode 2); k_bucket
+void launch_first(const BucketLaunch& L, hipStream_t s);
+void launch_fallback(const BucketLaunch& L, hipStream_t s);
+void launch_parked(const BucketLaunch& L, hipStream_t s);
 void launch_final(const BucketLaunch& L, hipStream_t s);
 // a batch of at most kPartTile ops after its one-block partition (k_part with
 // a touched list): every listed partition bucket's directory buckets through
 // the final pass, records walked in batch order (k_medium)
-void launch_medium(const BucketLaunch& L, const uint32_t* touched, hipStream_t s);
+void launch_medium(const BucketArgs& a, const uint32_t* touched, hipStream_t s);
 // a whole batch of n <= kChunkWave ops in one launch (k_mixed_small, k_mixed_tiny
 // up to 64); ops == null: insert-only.  a.st / a.vout are the outputs; inputs
 // may be host-mapped
-void launch_mixed_small(const BucketLaunch& L, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
+void launch_mixed_small(const BucketArgs& a, const uint8_t* ops, const uint64_t* keys, const uint64_t* vin,
                         hipStream_t s);
 
-// k_split: one wave per entry of the split list the apply pass granted (a
-// fixed grid looping over ctl->nsplit[par] entries; denied entries are ~0).
-// Built from the batch's BucketArgs (bucket.hip split_args).
+// k_split: a fixed grid looping over the splits the first pass requested, in
+// shard-major order (their count from the grant shards; a bucket that does not
+// fit is denied whole).  Built from the batch's BucketArgs (bucket.hip split_args).
 struct SplitArgs {
   uint32_t par;        // the batch's parity: its grant shards
   uint32_t pfix;       // small sub-directories grow in their fixed slots
@@ -418,8 +409,8 @@ struct SplitArgs {
   ulonglong2* drops;      // the drop log, or null
   uint32_t team_max;      // split lists up to this long go by teams of four waves (PMDFC_SPLIT_TEAM_MAX)
 };
-// one split round: split every segment the apply pass granted (it hands out
-// child ids / sub-directory space itself), one wave each (k_split)
+// the split round: every split the first pass requested, on the plan's grid
+// with its team_max (k_split grants child ids / sub-directory space itself)
 void launch_split_round(const BucketLaunch& L, hipStream_t s);
 
 // the persistent serving kernel of the per-op front-end (k_serve, a wave per ring)
