@@ -77,7 +77,9 @@ extern "C" {
  * pmdfc_cceh_erase does not undo it: Erase frees slots, which later Inserts
  * take through the occupancy words, but it never merges segments or returns
  * ids to the arena, and "the table stopped splitting" stays sticky across it
- * as well -- a window that is full after the erases still answers CAPACITY. */
+ * as well -- a window that is full after the erases still answers CAPACITY.
+ * pmdfc_cceh_compact does undo it when it merges a pair: the ids of merged
+ * segments return to the arena and the table splits again, content intact. */
 #define PMDFC_ST_FILTERED 7      /* bloom-negative: miss without an index probe */
 #define PMDFC_ST_WRONG_SHARD 8   /* key's hash prefix is owned by another shard */
 #define PMDFC_ST_ROUTE_OVERFLOW 9 /* routed batch: the owner's carry was full (carry_cap ops waiting), op not applied */
@@ -210,8 +212,9 @@ int pmdfc_cceh_find_anyway(pmdfc_cceh_t* t, const uint64_t* d_keys, uint64_t* d_
  * erased earlier in the batch), PMDFC_ST_RESERVED_KEY, PMDFC_ST_WRONG_SHARD.
  * n <= max_batch, else PMDFC_ERR_ARG.  Enqueues on `stream` and never
  * synchronises, except that the first call allocates its scratch.  It frees
- * slots and nothing else: segments are never merged, capacity, depth and the
- * directory stay, Utilization falls (see PMDFC_ST_CAPACITY).  Like snapshot it
+ * slots and nothing else: capacity, depth and the directory stay, Utilization
+ * falls (see PMDFC_ST_CAPACITY); merging the thinned segments and returning
+ * their ids to the arena is pmdfc_cceh_compact.  Like snapshot it
  * must not run beside the serving waves.  A batch that repeats one stored key
  * n times is applied by one wave as a run of n ops: slow but correct.  A
  * tripped loop guard of the shift (never seen) sets error_flags bit 17. */
@@ -381,6 +384,51 @@ int pmdfc_cceh_export_entries(pmdfc_cceh_t* t, uint64_t* d_keys, uint64_t* d_val
 /* Segments per block of the live-count scan both calls and the packed restore
  * run (tests cover tables of more segments than one block). */
 uint32_t pmdfc_cceh_packed_scan_block(void);
+
+/* ---- Compact: merge sibling segments, reclaim the arena (synchronous) ----
+ * The inverse of Segment::Split, which the reference never needs (DESIGN.md
+ * 4.9).  Serially: while some pair of sibling leaves qualifies, merge it.
+ * Siblings are two segments of one local depth L > initial_depth whose hash
+ * prefixes are 2q and 2q + 1.  A pair qualifies when its two segments hold at
+ * most fill_limit entries together and the replay drops nothing: the parent
+ * (depth L - 1, prefix q) is child 0's image unchanged; child 1's entries, in
+ * slot order from the slot after its highest empty one (cyclically, so every
+ * cluster is walked from its true start), go each to the first free slot of
+ * their 32-slot window; an entry that finds its window full refuses the pair,
+ * whose children stay byte for byte.  The fixpoint does not depend on the
+ * order the pairs are taken in.  Every stored pair stays stored once per
+ * copy; Get and FindAnyway of every key answer as before; no segment ends
+ * below initial_depth; a second Compact with the same limit merges nothing.
+ * fill_limit: 1..1024, 0 means 512, above 1024 PMDFC_ERR_ARG.
+ * Like snapshot and restore the call synchronises the device, runs under the
+ * table's lock and must not run beside the serving waves.  While the merges
+ * are decided the table is untouched.  merges == 0: it stays untouched -- no
+ * restore runs, the history counters stay, "the table stopped splitting"
+ * (PMDFC_ST_CAPACITY) stays.  Otherwise the table is rebuilt from the merged
+ * image with the effects of pmdfc_cceh_restore: the history counters and
+ * error_flags restart, the table splits again, segment ids are dense
+ * (segments == segments_after, none retired), and the bucket resolution may
+ * fall and ramp again.  Failures before that step leave the table as it was:
+ * PMDFC_ERR_NOMEM (the working image), PMDFC_ERR_SIZE (the rebuilt
+ * sub-directories do not fit the pool).
+ * Peak device memory: one version-1 image of the table (16 KiB per segment)
+ * plus about 40 bytes of rows and scan words per segment.  With uniformly hashed
+ * keys Compact does not raise the total capacity: it hands ids from cold
+ * prefixes back to the arena for the hot ones. */
+typedef struct pmdfc_compact_result {
+  uint64_t segments_before, segments_after;
+  uint64_t merges;   /* pairs merged, all rounds */
+  uint64_t refused;  /* sibling leaf pairs of the FINAL table within fill_limit whose replay would drop */
+  uint32_t rounds, depth_before, depth_after, reserved;
+} pmdfc_compact_result_t;
+int pmdfc_cceh_compact(pmdfc_cceh_t* t, uint32_t fill_limit, pmdfc_compact_result_t* out, void* stream);
+/* The steps of the last pmdfc_cceh_compact that ran its rounds, in
+ * milliseconds between HIP events on its stream: ms[0] canonical order and
+ * live counts, ms[1] the gather, ms[2] the restore (0 if nothing merged), ms[3
+ * ...] the rounds in order, the last of them the one that merged nothing.
+ * *n_out: the number of steps (0: no such call yet); ms == NULL or cap too
+ * small: PMDFC_ERR_SIZE with *n_out set. */
+int pmdfc_cceh_compact_timing(pmdfc_cceh_t* t, float* ms, uint32_t cap, uint32_t* n_out);
 
 /* ---- kernel timing (HIP events on the launching stream) -------------- */
 /* kernel classes */

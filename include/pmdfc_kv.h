@@ -87,6 +87,11 @@ int64_t pmdfc_kv_ops_async(pmdfc_kv_t* kv, const uint8_t* ops, const uint64_t* k
  * (>= 0), or < 0 on an argument error. */
 int pmdfc_kv_erase(pmdfc_kv_t* kv, uint64_t key, uint8_t* status);
 int64_t pmdfc_kv_erase_run(pmdfc_kv_t* kv, const uint64_t* keys, uint8_t* status, uint64_t n);
+/* pmdfc_cceh_compact after every queued op, with the serving waves stopped
+ * (they start again when ops wait): sibling segments that fit one segment are
+ * merged and their ids return to the arena.  The stored keys do not change:
+ * an attached counting BF needs nothing. */
+int pmdfc_kv_compact(pmdfc_kv_t* kv, uint32_t fill_limit, pmdfc_compact_result_t* out);
 /* wait for every op queued before the call */
 int pmdfc_kv_flush(pmdfc_kv_t* kv);
 

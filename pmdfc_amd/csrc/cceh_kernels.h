@@ -164,6 +164,9 @@ struct ScatterArgs {
   const uint32_t* occ_img;
   const uint64_t* base;
   uint64_t live;
+  // A compacted working image (compact.hip), else src == nullptr: canonical
+  // segment i is segment src[i] of img (a version-1 pairs region with gaps).
+  const uint32_t* src;
 };
 // segment i of the image -> arena id i: pairs, occupancy words, local depth,
 // its directory entries; the live keys are hashed against the segment's prefix
@@ -201,6 +204,23 @@ struct PackArgs {
   uint32_t* bad;
 };
 void launch_image_pack(const PackArgs& a, uint32_t nseg, hipStream_t s);
+// compact.hip (pmdfc_cceh_compact): one round of sibling
+// merges inside a gathered version-1 pairs region.  The rows are indexed by
+// the ORIGINAL canonical index and never move; a merged pair lives on in its
+// left child's row and image slot, the right child's row is marked dead.
+constexpr uint32_t kCompactDead = 0xFFu;  // ld[i] & 0xFF of a segment merged into its left sibling
+struct CompactArgs {
+  ulonglong2* img;     // nseg x 1024 pairs in canonical order
+  uint32_t* ld;        // local depth | the round that made the segment << 8 (0: as gathered)
+  const uint32_t* pos; // the segment's start in the hash space, in units of 2^-30 (never changes for a left child)
+  uint32_t* cnt;       // live entries (launch_image_live_scan)
+  uint32_t* next;      // the next live index (nseg: none)
+  uint32_t* refused;   // sticky: the pair (i, next[i]) drops in the replay, its leaves never change
+  uint32_t* merged;    // += 1 per pair merged in this round
+  uint32_t nseg, d0, fill_limit;
+  uint32_t round;      // 1, 2, ...
+};
+void launch_compact_merge(const CompactArgs& a, hipStream_t s);
 // flatten the bucketed directory for pure-Get batches: *bits = p1 + max db
 // (the physical depth), flat[x] = the sub-directory entry of index x
 void launch_flatten(const uint64_t* hdr, const uint32_t* pool, uint32_t p1, uint32_t* flat,

@@ -227,6 +227,8 @@ struct pmdfc_cceh {
     uint32_t sort_bits = 0;
   } er;
 
+  std::vector<float> compact_ms;  // the last Compact's steps (pmdfc_cceh_compact_timing)
+
   pmdfc::Geo geo() const { return pmdfc::Geo{hdr, pool, p1, sbits, shard, nullptr, nullptr}; }
   pmdfc::Geo geo_flat() const { return pmdfc::Geo{hdr, pool, p1, sbits, shard, gflat, gflat_bits}; }
 };

@@ -7,7 +7,8 @@
 // Restore: k_image_ctl starts the control block and the per-batch words as a
 // reset does, k_image_scatter copies canonical segment i to arena id i,
 // rebuilds its occupancy words, local depth and directory entries, and checks
-// every live key against the segment's hash prefix.
+// every live key against the segment's hash prefix (k_image_scatter_sel: the
+// same from segment src[i] of a compacted working image, compact.hip).
 // The packed image (packed_image.h) and pmdfc_cceh_export_entries leave the
 // empty slots out: k_image_live_count / _sums / _scan / _base give every
 // canonical segment the number of entries stored before it, from occupancy
@@ -184,6 +185,20 @@ __device__ __forceinline__ void scatter_segment(const ScatterArgs& a, uint32_t i
 __global__ __launch_bounds__(256) void k_image_scatter(ScatterArgs a) {
   const uint32_t i = blockIdx.x;
   const ulonglong2* src = a.img + (size_t)i * kSlots;
+  ulonglong2 p[4];
+  bool live[4];
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) p[k] = ld_pair_l2(src + k * 256u + threadIdx.x);
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) live[k] = p[k].x != kInvalid;
+  scatter_segment(a, i, p, live);
+}
+
+// a compacted working image (compact.hip): canonical segment i is the whole
+// segment src[i] of the image
+__global__ __launch_bounds__(256) void k_image_scatter_sel(ScatterArgs a) {
+  const uint32_t i = blockIdx.x;
+  const ulonglong2* src = a.img + (size_t)a.src[i] * kSlots;
   ulonglong2 p[4];
   bool live[4];
 #pragma unroll
@@ -404,6 +419,8 @@ void launch_image_scatter(const ScatterArgs& a, hipStream_t s) {
   if (!a.nseg) return;
   if (a.occ_img)
     hipLaunchKernelGGL(k_image_unpack, dim3(a.nseg), dim3(256), 0, s, a);
+  else if (a.src)
+    hipLaunchKernelGGL(k_image_scatter_sel, dim3(a.nseg), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(k_image_scatter, dim3(a.nseg), dim3(256), 0, s, a);
 }

@@ -12,6 +12,7 @@
 #include "engine_state.h"
 #include "host_common.h"
 #include "image.h"
+#include "image_host.h"
 #include "packed_image.h"
 
 using namespace pmdfc;
@@ -79,12 +80,8 @@ int pmdfc_cceh_snapshot(pmdfc_cceh_t* t, void* buf, uint64_t cap_bytes, uint64_t
   return PMDFC_OK;
 }
 
-// The part of a restore that both image kinds share, from a header and local
-// depths that validation accepted and nseg <= max_segments: the directory's
-// fit (still the table untouched), then the table becomes the image's.  `a`
-// arrives with the image's own fields set (img; for a packed image occ_img,
-// base, live).
-static int restore_table(pmdfc_cceh_t* t, hipStream_t s, const image::Header& h, const std::vector<uint8_t>& ld,
+// (image_host.h)
+int pmdfc::restore_table(pmdfc_cceh* t, hipStream_t s, const image::Header& h, const std::vector<uint8_t>& ld,
                          ScatterArgs a) {
   const uint32_t nseg = (uint32_t)h.nseg;
   // the directory: the bucket bits rebucket_now would have reached, each
@@ -156,33 +153,6 @@ static int restore_table(pmdfc_cceh_t* t, hipStream_t s, const image::Header& h,
   return PMDFC_OK;
 }
 
-namespace {
-// the device scratch of launch_image_live_scan for nseg segments, and a word
-// for what a pack counts
-struct LiveWork {
-  DevTmp mem;
-  LiveScan w{};
-  uint32_t* bad = nullptr;
-  int alloc(uint32_t nseg) {
-    const uint64_t nblk = live_scan_blocks(nseg);
-    HIPCHK(hipMalloc(&mem.p, (nseg + 2 * nblk + 1) * sizeof(uint64_t) + ((uint64_t)nseg + 1) * sizeof(uint32_t)));
-    w.base = static_cast<uint64_t*>(mem.p);
-    w.sums = w.base + nseg;
-    w.offs = w.sums + nblk;
-    w.cnt = reinterpret_cast<uint32_t*>(w.offs + nblk + 1);
-    bad = w.cnt + nseg;
-    return PMDFC_OK;
-  }
-  // (after launch_image_live_scan on s) the grand total, read back
-  int total(uint32_t nseg, hipStream_t s, uint64_t* out) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, w.offs + live_scan_blocks(nseg), sizeof *out, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return PMDFC_OK;
-  }
-};
-}  // namespace
-
 // pmdfc_cceh_restore of a packed image (packed_image.h); hb: its header bytes
 static int restore_packed(pmdfc_cceh_t* t, hipStream_t s, const uint8_t* in, uint64_t bytes,
                           const std::vector<uint8_t>& hb) {
@@ -252,21 +222,8 @@ int pmdfc_cceh_restore(pmdfc_cceh_t* t, const void* buf, uint64_t bytes, void* s
 
 // ---- packed image and entry export (packed_image.h, image.hip)
 
-namespace {
-// Canonical order on the device for one synchronous call: order[i] the
-// directory entry of canonical segment i, ld[i] its local depth, and from the
-// engine's occupancy words base[i], the entries stored before segment i, and
-// their total.
-struct Canon {
-  DevTmp wk, ord;
-  LiveWork lw;
-  uint32_t nseg = 0;
-  uint32_t* order = nullptr;
-  uint8_t* ld = nullptr;
-  uint64_t live = 0;
-};
-
-int canonical_live(pmdfc_cceh_t* t, hipStream_t s, Canon& c) {
+// (image_host.h)
+int pmdfc::canonical_live(pmdfc_cceh* t, hipStream_t s, Canon& c) {
   const uint32_t nb = 1u << t->p1;
   HIPCHK(hipMalloc(&c.wk.p, (2ull * nb + 1) * sizeof(uint32_t)));
   uint32_t* cnt = static_cast<uint32_t*>(c.wk.p);
@@ -287,7 +244,6 @@ int canonical_live(pmdfc_cceh_t* t, hipStream_t s, Canon& c) {
   if (c.live > (uint64_t)c.nseg * kSlots) return fail(PMDFC_ERR_STATE, "the occupancy words count more than the slots");
   return PMDFC_OK;
 }
-}  // namespace
 
 uint32_t pmdfc_cceh_packed_scan_block(void) { return kLiveScanBlock; }
 

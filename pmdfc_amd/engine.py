@@ -64,6 +64,13 @@ class Stats(C.Structure):
                 ("error_flags", C.c_uint32), ("fast_declined", C.c_uint32)]
 
 
+class CompactResult(C.Structure):
+    """pmdfc_compact_result_t"""
+    _fields_ = [("segments_before", C.c_uint64), ("segments_after", C.c_uint64), ("merges", C.c_uint64),
+                ("refused", C.c_uint64), ("rounds", C.c_uint32), ("depth_before", C.c_uint32),
+                ("depth_after", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/pmdfc_cceh.h declares (checked by tests/test_capi.py)
 EXPORTS = [
     "pmdfc_depth_for_hybrid", "pmdfc_depth_for_src", "pmdfc_abi_version", "pmdfc_last_error",
@@ -90,6 +97,7 @@ EXPORTS = [
     "pmdfc_cceh_snapshot_packed", "pmdfc_cceh_export_entries", "pmdfc_cceh_packed_scan_block",
     "pmdfc_cbf_rebuild", "pmdfc_cbf_audit",
     "pmdfc_cceh_erase",
+    "pmdfc_cceh_compact", "pmdfc_cceh_compact_timing",
 ]
 
 
@@ -190,6 +198,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_cceh_export_entries": (i32, [P, P, P, u64, C.POINTER(u64), P]),
         "pmdfc_cceh_packed_scan_block": (u32, []),
         "pmdfc_cceh_erase": (i32, [P, P, P, u64, P]),
+        "pmdfc_cceh_compact": (i32, [P, u32, C.POINTER(CompactResult), P]),
+        "pmdfc_cceh_compact_timing": (i32, [P, P, u32, C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -485,8 +495,8 @@ class CCEH:
         """Remove every stored copy of each key (pmdfc_cceh_erase), in batch
         order.  Returns the statuses: ST_ERASED, ST_MISS for a key not stored
         at its turn, ST_RESERVED_KEY, ST_WRONG_SHARD.  Freed slots are taken
-        by later Inserts; segments are never merged, so Capacity stays and
-        Utilization falls.  More than max_batch keys go as consecutive
+        by later Inserts; Capacity stays and Utilization falls until Compact
+        merges the thinned segments.  More than max_batch keys go as consecutive
         batches, which gives the same table and statuses as one."""
         dev_in = isinstance(keys, torch.Tensor)
         k = self._d.u64(keys)
@@ -496,6 +506,31 @@ class CCEH:
             _check(load_library().pmdfc_cceh_erase(self._h, k[off:].data_ptr(), st[off:].data_ptr(), m,
                                                    self._d.stream()), "pmdfc_cceh_erase")
         return st if dev_in else _host_out(st, "u8")
+
+    def Compact(self, fill_limit: int = 512) -> dict:
+        """Merge sibling segments that hold at most fill_limit entries together
+        and whose replay into one segment drops nothing, to the fixpoint, and
+        return their ids to the arena (pmdfc_cceh_compact).
+        Every stored pair stays and every Get answers as before.  Returns the
+        counts: segments_before / _after, merges, refused (pairs within the
+        limit whose replay would drop), rounds, depth_before / _after.  With no
+        merge the table is untouched; otherwise it is rebuilt as restore()
+        rebuilds one: the history counters of stats() restart and a table that
+        had answered ST_CAPACITY splits again.  Synchronous."""
+        r = CompactResult()
+        _check(load_library().pmdfc_cceh_compact(self._h, fill_limit, C.byref(r), self._d.stream()),
+               "pmdfc_cceh_compact")
+        return {n: getattr(r, n) for n, _ in CompactResult._fields_ if n != "reserved"}
+
+    def compact_timing(self) -> dict:
+        """The steps of the last Compact that ran its rounds, in ms of HIP
+        events: canonical (order and live counts), gather, restore, rounds (a
+        list, the last the round that merged nothing)."""
+        ms = (C.c_float * 64)()
+        n = C.c_uint32()
+        _check(load_library().pmdfc_cceh_compact_timing(self._h, ms, 64, C.byref(n)), "compact_timing")
+        v = list(ms[:n.value])
+        return {"canonical": v[0], "gather": v[1], "restore": v[2], "rounds": v[3:]} if v else {}
 
     def Recovery(self) -> bool:
         """CCEH::Recovery (CCEH_hybrid.cpp:391-410) repairs directory entries of

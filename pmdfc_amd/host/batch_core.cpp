@@ -1081,6 +1081,17 @@ uint8_t BatchCore::Erase(uint64_t key) {
   return st;
 }
 
+int BatchCore::Compact(uint32_t fill_limit, pmdfc_compact_result_t* out) {
+  if (!out) return PMDFC_ERR_ARG;
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t st) {
+        rc = pmdfc_cceh_compact(t_, fill_limit, out, st);
+        if (rc != PMDFC_OK) set_error(std::string("Compact: ") + pmdfc_last_error());
+      }))
+    return PMDFC_ERR_STATE;
+  return rc;
+}
+
 int BatchCore::Stats(pmdfc_cceh_stats_t* out) {
   int rc = PMDFC_ERR_STATE;
   if (!with_engine([&](hipStream_t) { rc = pmdfc_cceh_stats(t_, out); })) return PMDFC_ERR_STATE;

@@ -39,7 +39,7 @@
 // queued and a callback runs on the control thread when its result is back.
 //
 // Calls that need the whole engine (Utilization, Capacity, FindAnyway, Erase
-// and EraseRun, the counting-BF pack, attach, rebuild and audit, Save and
+// and EraseRun, Compact, the counting-BF pack, attach, rebuild and audit, Save and
 // Load) wait for every
 // op queued before them, stop the device wave, run on the engine's stream,
 // and start it again.
@@ -166,6 +166,13 @@ class BatchCore {
   // keys answered kBatchFailed.
   uint8_t Erase(uint64_t key);
   uint64_t EraseRun(const uint64_t* keys, uint8_t* status, uint64_t n);
+
+  // ---- pmdfc_cceh_compact: sibling segments that fit one segment merged to
+  // the fixpoint, their ids back in the arena.  A whole-engine
+  // call like the two above: after every op enqueued so far, the waves
+  // stopped.  The stored keys do not change, so an attached counting BF needs
+  // nothing.  PMDFC_ERR_STATE from a completion callback (nothing done).
+  int Compact(uint32_t fill_limit, pmdfc_compact_result_t* out);
 
   // ---- counting BF of KV (server/KV.cpp:113-121).  The filter must live on
   // the same device and outlive the core's use of it.

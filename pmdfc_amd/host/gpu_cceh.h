@@ -82,6 +82,9 @@ class GpuCCEH : public IHash {
   int EraseBatch(const uint64_t* keys, uint8_t* status, uint64_t n) {
     return core_.EraseRun(keys, status, n) ? PMDFC_ERR_STATE : PMDFC_OK;
   }
+  // Sibling segments that fit one segment merged, their ids back in the arena
+  // (BatchCore::Compact, pmdfc_cceh_compact); every stored pair stays.
+  int Compact(uint32_t fill_limit, pmdfc_compact_result_t* out) { return core_.Compact(fill_limit, out); }
   Value_t Get(Key_t& key) override {  // NONE on a miss (and on a failed op)
     uint64_t v = 0;
     return core_.Get(key, &v) == PMDFC_ST_HIT ? reinterpret_cast<Value_t>(v) : NONE;

@@ -19,7 +19,7 @@ import os
 
 import numpy as np
 
-from .engine import OP_GET, OP_INSERT, PMDFC_ERR_SIZE, ST_HIT, PmdfcError, Stats, _require_gpu, depth_for_hybrid, depth_for_src, load_library
+from .engine import OP_GET, OP_INSERT, PMDFC_ERR_SIZE, ST_HIT, CompactResult, PmdfcError, Stats, _require_gpu, depth_for_hybrid, depth_for_src, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 KV_LIB_PATH = os.path.join(_HERE, "lib", "libpmdfc_gpucceh.so")
@@ -32,7 +32,7 @@ KV_EXPORTS = [
     "pmdfc_kv_find_anyway", "pmdfc_kv_stats", "pmdfc_kv_dump", "pmdfc_kv_phase", "pmdfc_kv_last_error",
     "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_save_packed", "pmdfc_kv_load",
     "pmdfc_kv_attach_cbf", "pmdfc_kv_rebuild_cbf", "pmdfc_kv_audit_cbf",
-    "pmdfc_kv_erase", "pmdfc_kv_erase_run",
+    "pmdfc_kv_erase", "pmdfc_kv_erase_run", "pmdfc_kv_compact",
 ]
 
 _kvlib = None
@@ -78,6 +78,7 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_last_error": (C.c_char_p, [P]),
         "pmdfc_kv_erase": (i32, [P, u64, P]),
         "pmdfc_kv_erase_run": (i64, [P, P, P, u64]),
+        "pmdfc_kv_compact": (i32, [P, u32, C.POINTER(CompactResult)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -220,6 +221,16 @@ class KV:
         if rc < 0:
             self._err("erase_run", rc)
         return st
+
+    def compact(self, fill_limit: int = 512) -> dict:
+        """CCEH.Compact after every queued op, with the serving waves stopped
+        -> its counts.  The stored keys do not change: an attached counting BF
+        needs nothing."""
+        r = CompactResult()
+        rc = load_kv_library().pmdfc_kv_compact(self._h, fill_limit, C.byref(r))
+        if rc != 0:
+            self._err("compact", rc)
+        return {n: getattr(r, n) for n, _ in CompactResult._fields_ if n != "reserved"}
 
     def stats(self) -> dict:
         s = Stats()
