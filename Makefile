@@ -5,7 +5,7 @@ CSRC := pmdfc_amd/csrc
 LIBDIR := pmdfc_amd/lib
 LIB := $(LIBDIR)/libpmdfc_cceh.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result
-SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/part.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/compact.hip $(CSRC)/cceh_engine.hip $(CSRC)/image_host.hip $(CSRC)/compact_host.hip $(CSRC)/route_host.hip $(CSRC)/filter_host.hip $(CSRC)/trace_host.hip $(CSRC)/extent_host.hip $(CSRC)/dist_host.hip
+SRCS := $(CSRC)/cceh_kernels.hip $(CSRC)/part.hip $(CSRC)/bucket.hip $(CSRC)/bloom.hip $(CSRC)/ubench.hip $(CSRC)/route.hip $(CSRC)/cbf.hip $(CSRC)/trace.hip $(CSRC)/extent.hip $(CSRC)/image.hip $(CSRC)/erase.hip $(CSRC)/match.hip $(CSRC)/compact.hip $(CSRC)/cceh_engine.hip $(CSRC)/image_host.hip $(CSRC)/compact_host.hip $(CSRC)/route_host.hip $(CSRC)/filter_host.hip $(CSRC)/trace_host.hip $(CSRC)/extent_host.hip $(CSRC)/dist_host.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/obj/%.o,$(SRCS))
 
 HOSTLIB := $(LIBDIR)/libpmdfc_gpucceh.so
@@ -17,8 +17,9 @@ BFKVTEST := $(LIBDIR)/test_gpu_filter_kv
 PAKKVTEST := $(LIBDIR)/test_gpu_packed_kv
 ERASEKVTEST := $(LIBDIR)/test_gpu_erase_kv
 COMPACTKVTEST := $(LIBDIR)/test_gpu_compact_kv
+MATCHKVTEST := $(LIBDIR)/test_gpu_match_kv
 
-all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(ERASEKVTEST) $(COMPACTKVTEST) $(FRONTBENCH) oracle
+all: $(LIB) $(HOSTLIB) $(KVTEST) $(IMGKVTEST) $(BFKVTEST) $(PAKKVTEST) $(ERASEKVTEST) $(COMPACTKVTEST) $(MATCHKVTEST) $(FRONTBENCH) oracle
 
 # (the compiler writes each object's header dependencies beside it: obj/%.d)
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip
@@ -50,6 +51,9 @@ $(ERASEKVTEST): tests/cpp/test_gpu_erase_kv.cpp $(HOSTLIB)
 
 $(COMPACTKVTEST): tests/cpp/test_gpu_compact_kv.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_compact_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
+
+$(MATCHKVTEST): tests/cpp/test_gpu_match_kv.cpp $(HOSTLIB)
+	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tests/cpp/test_gpu_match_kv.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'
 
 $(FRONTBENCH): tools/bench_frontend.cpp $(HOSTLIB)
 	$(HIPCC) -O2 -std=c++17 -Wall -o $@ tools/bench_frontend.cpp -L$(LIBDIR) -lpmdfc_gpucceh -lpmdfc_cceh -lpthread -Wl,-rpath,'$$ORIGIN'

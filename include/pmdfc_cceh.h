@@ -219,6 +219,46 @@ int pmdfc_cceh_find_anyway(pmdfc_cceh_t* t, const uint64_t* d_keys, uint64_t* d_
  * n times is applied by one wave as a run of n ops: slow but correct.  A
  * tripped loop guard of the shift (never seen) sets error_flags bit 17. */
 int pmdfc_cceh_erase(pmdfc_cceh_t* t, const uint64_t* d_keys, uint8_t* d_status, uint64_t n, void* stream);
+/* EraseMatching: every stored entry whose key k satisfies
+ * (k & mask) == (d_patterns[i] & mask) for some i < n is removed, with every
+ * copy of its key, in one scan of the table.  It stands in
+ * for the two cleancache invalidations the reference leaves empty
+ * (pmdfc_cleancache_flush_inode and pmdfc_cleancache_flush_fs,
+ * client/tcp_style/pmdfc.c:467-487): the clients build every key as
+ * inode << 32 | page index, so an inode is the pattern inode << 32 under the
+ * mask 0xFFFFFFFF00000000, and mask 0 with any one pattern empties the table.
+ * The contract is Erase's serial rule (above): let L be the distinct stored
+ * keys that match, ordered by canonical segment order and inside a segment by
+ * slot order of the table before the call, a key stored several times taken
+ * once at its first copy; the table afterwards is the table before with
+ * Erase(L[0]), Erase(L[1]), ... applied.  So every stored entry again has no
+ * empty slot between its window's start and itself before the call returns,
+ * and the entries that do not match answer every probe as before, their
+ * copies in the same order.
+ * n <= PMDFC_MATCH_MAX, else PMDFC_ERR_ARG; a null d_patterns with n > 0 is
+ * PMDFC_ERR_ARG too; either way the table is untouched.  n == 0 removes
+ * nothing and scans nothing (a result of zeroes).  Patterns may repeat; any
+ * 64-bit value is a pattern, 0 and ~0 included; an empty slot never matches,
+ * whatever the pattern.  d_patterns is device memory.  `out` may be null.
+ * Like Erase it frees slots and nothing else: local depths, the directory,
+ * the segment count, the history counters of pmdfc_cceh_stats and a sticky
+ * PMDFC_ST_CAPACITY state all stay; Capacity stays, Utilization falls, the
+ * freed slots go to later Inserts and pmdfc_cceh_compact gives the space
+ * back.  A segment none of whose keys match is only read; one whose every
+ * live key matches is cleared wholesale (segments_cleared).  A sharded engine
+ * removes what it stores: the pattern does not say where a key lives, so
+ * every rank calls it on its own engine.  Synchronous, under the table's
+ * lock; like snapshot and Erase it must not run beside the serving waves.  A
+ * tripped loop guard (never seen) sets error_flags bit 17. */
+#define PMDFC_MATCH_MAX 1024
+typedef struct pmdfc_erase_matching_result {
+  uint64_t removed;            /* entries taken out, every copy counted */
+  uint32_t segments_scanned;   /* arena ids visited: min(nsegs, max_segments); 0 when n == 0 */
+  uint32_t segments_changed;   /* segments that lost at least one entry */
+  uint32_t segments_cleared;   /* of those, the ones emptied wholesale */
+} pmdfc_erase_matching_result_t;
+int pmdfc_cceh_erase_matching(pmdfc_cceh_t* t, uint64_t mask, const uint64_t* d_patterns, uint32_t n,
+                              pmdfc_erase_matching_result_t* out, void* stream);
 /* Interleaved Insert/Get in batch order; a Get observes exactly the inserts
  * before it in the batch.  d_values_in is read for inserts, d_values_out is
  * written for gets (0 for inserts and misses).  Small and medium batches take

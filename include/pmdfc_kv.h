@@ -87,6 +87,17 @@ int64_t pmdfc_kv_ops_async(pmdfc_kv_t* kv, const uint8_t* ops, const uint64_t* k
  * (>= 0), or < 0 on an argument error. */
 int pmdfc_kv_erase(pmdfc_kv_t* kv, uint64_t key, uint8_t* status);
 int64_t pmdfc_kv_erase_run(pmdfc_kv_t* kv, const uint64_t* keys, uint8_t* status, uint64_t n);
+/* pmdfc_cceh_erase_matching after every queued op, with the serving waves
+ * stopped (they start again when ops wait): every stored key k with
+ * (k & mask) == (patterns[i] & mask) for some i < n goes, in one scan of the
+ * table.  patterns is host memory, n <= PMDFC_MATCH_MAX (else PMDFC_ERR_ARG).
+ * What a server calls for the cleancache hooks the reference leaves empty:
+ * invalidate_inode(ino) is the pattern ino << 32 under the mask
+ * 0xFFFFFFFF00000000, invalidate_fs is mask 0 with any one pattern.  When it
+ * removed something and a counting BF is attached, the filter is rebuilt from
+ * the table under the same stop (exact, duplicates included).  out nullable. */
+int pmdfc_kv_erase_matching(pmdfc_kv_t* kv, uint64_t mask, const uint64_t* patterns, uint32_t n,
+                            pmdfc_erase_matching_result_t* out);
 /* pmdfc_cceh_compact after every queued op, with the serving waves stopped
  * (they start again when ops wait): sibling segments that fit one segment are
  * merged and their ids return to the arena.  The stored keys do not change:

@@ -854,6 +854,47 @@ int pmdfc_cceh_erase(pmdfc_cceh_t* t, const uint64_t* keys, uint8_t* st, uint64_
   return PMDFC_OK;
 }
 
+// EraseMatching (match.hip): one launch, then the four result
+// words come back.  Synchronous.
+int pmdfc_cceh_erase_matching(pmdfc_cceh_t* t, uint64_t mask, const uint64_t* d_patterns, uint32_t n,
+                              pmdfc_erase_matching_result_t* out, void* stream) {
+  if (!t || (n && !d_patterns)) return fail(PMDFC_ERR_ARG, "null argument");
+  if (n > PMDFC_MATCH_MAX) return fail(PMDFC_ERR_ARG, "n > PMDFC_MATCH_MAX");
+  if (out) *out = pmdfc_erase_matching_result_t{};
+  if (n == 0) return PMDFC_OK;
+  std::lock_guard<std::mutex> lk(t->mu);
+  DevGuard g(t->dev);
+  hipStream_t s = (hipStream_t)stream;
+  if (!t->match_out) {
+    void* w = nullptr;
+    HIPCHK(hipMalloc(&w, 4 * sizeof(unsigned long long)));
+    t->dev_allocs.push_back(w);
+    t->match_out = static_cast<unsigned long long*>(w);
+  }
+  HIPCHK(hipMemsetAsync(t->match_out, 0, 4 * sizeof(unsigned long long), s));
+  MatchArgs a{};
+  a.mask = mask;
+  a.patterns = d_patterns;
+  a.n = n;
+  a.pairs = t->pairs;
+  a.occ = t->occ;
+  a.ctl = t->ctl;
+  a.max_segs = (uint32_t)t->max_segs;
+  a.out = t->match_out;
+  launch_erase_matching(a, s);
+  HIPCHK(hipGetLastError());
+  unsigned long long h[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h, t->match_out, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (out) {
+    out->removed = h[0];
+    out->segments_changed = (uint32_t)h[1];
+    out->segments_cleared = (uint32_t)h[2];
+    out->segments_scanned = (uint32_t)h[3];
+  }
+  return PMDFC_OK;
+}
+
 int pmdfc_cceh_get_records(pmdfc_cceh_t* t, const uint64_t* keys, uint64_t* resp, uint64_t n, void* stream) {
   if (!t || (n && (!keys || !resp))) return fail(PMDFC_ERR_ARG, "null argument");
   return do_get(t, keys, resp, nullptr, n, stream);

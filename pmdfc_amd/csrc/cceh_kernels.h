@@ -509,6 +509,21 @@ struct EraseArgs {
 hipError_t erase_sort_temp_bytes(uint64_t max_batch, uint32_t sort_bits, size_t* bytes);
 hipError_t launch_erase(const EraseArgs& a, hipStream_t s);
 
+// match.hip (EraseMatching): one launch over arena ids
+// [0, min(ctl->nsegs, max_segs)), a wave per segment; a tripped guard sets
+// kErrEraseGuard.  out is not zeroed here.
+struct MatchArgs {
+  uint64_t mask;
+  const uint64_t* patterns;  // n, device memory
+  uint32_t n;                // 1 .. PMDFC_MATCH_MAX
+  ulonglong2* pairs;
+  uint32_t* occ;
+  DevCtl* ctl;
+  uint32_t max_segs;
+  unsigned long long* out;   // [0] += entries removed, [1] += segments changed, [2] += segments cleared, [3] = ids visited
+};
+void launch_erase_matching(const MatchArgs& a, hipStream_t s);
+
 // trace.hip (replay_KV trace ingestion)
 struct TraceLine {
   uint64_t key;  // (inode << 32) + offset

@@ -227,6 +227,8 @@ struct pmdfc_cceh {
     uint32_t sort_bits = 0;
   } er;
 
+  unsigned long long* match_out = nullptr;  // EraseMatching's four result words (allocated by the first call)
+
   std::vector<float> compact_ms;  // the last Compact's steps (pmdfc_cceh_compact_timing)
 
   pmdfc::Geo geo() const { return pmdfc::Geo{hdr, pool, p1, sbits, shard, nullptr, nullptr}; }

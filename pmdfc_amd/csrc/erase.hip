@@ -32,6 +32,7 @@
 // repeats one stored key n times gives one wave a run of n ops: slow, correct.
 #include "cceh_device.h"
 #include "cceh_kernels.h"
+#include "erase_device.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -90,15 +91,14 @@ __global__ __launch_bounds__(256) void k_erase_heads(const uint32_t* __restrict_
 }
 
 // One wave per listed run, the run's ops in batch order, the rule above per
-// op with all 64 lanes.  The wave owns the segment and its occupancy row;
-// it reads back what it wrote, so pairs are loaded through L2 (ld_pair_l2) and
-// its stores are drained before the next probe.
+// op with all 64 lanes (erase_key, erase_device.h).  The wave owns the segment
+// and its occupancy row; it reads back what it wrote, so pairs are loaded
+// through L2 (ld_pair_l2) and its stores are drained before the next probe.
 __global__ __launch_bounds__(256) void k_erase_apply(EraseArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
   const uint32_t nwaves = gridDim.x * 4u;
   const uint32_t nruns = *a.cursor;
-  const bool lo = lane < kWindow;
   bool trip = false;
   for (uint32_t r = wave; r < nruns; r += nwaves) {
     uint32_t j = a.work[r];
@@ -108,48 +108,7 @@ __global__ __launch_bounds__(256) void k_erase_apply(EraseArgs a) {
     for (; j < a.n && a.seg_out[j] == seg; ++j) {
       const uint32_t op = a.idx_out[j];
       const uint64_t key = a.keys[op];
-      const uint32_t w = (uint32_t)(hash64(key) & 0xFF) * 4u;
-      bool erased = false;
-      for (uint32_t copies = 0;; ++copies) {
-        // 1. the window in probe order, up to its first empty slot
-        ulonglong2 pr = make_ulonglong2(kInvalid, 0ULL);
-        if (lo) pr = ld_pair_l2(sp + ((w + lane) & (kSlots - 1)));
-        const uint32_t em = (uint32_t)__ballot(lo && pr.x == kInvalid);
-        uint32_t mm = (uint32_t)__ballot(lo && pr.x == key);
-        if (em) mm &= (1u << __builtin_ctz(em)) - 1u;
-        if (!mm) break;
-        if (copies >= kWindow) {  // (cannot happen: a window holds 32 copies at most)
-          trip = true;
-          break;
-        }
-        erased = true;
-        // 2. the first match
-        uint32_t p = (w + (uint32_t)__builtin_ctz(mm)) & (kSlots - 1);
-        // 3. backward shift: lane l looks at slot p + l
-        for (uint32_t step = 0;; ++step) {
-          const bool in = lane >= 1u && lo;
-          const uint32_t slot = (p + lane) & (kSlots - 1);
-          ulonglong2 c = make_ulonglong2(kInvalid, 0ULL);
-          if (in) c = ld_pair_l2(sp + slot);
-          const uint32_t ce = (uint32_t)__ballot(in && c.x == kInvalid);
-          const uint32_t home = (uint32_t)(hash64(c.x) & 0xFF) * 4u;
-          uint32_t ok = (uint32_t)__ballot(in && c.x != kInvalid && ((slot - home) & (kSlots - 1)) >= lane);
-          if (ce) ok &= (1u << __builtin_ctz(ce)) - 1u;
-          if (!ok || step >= kSlots) {
-            if (ok) trip = true;  // (cannot happen: the hole advances, an entry moves back 31 slots at most)
-            if (lane == 0) {
-              sp[p] = make_ulonglong2(kInvalid, 0ULL);
-              atomicAnd(&row[p >> 5], ~(1u << (p & 31u)));
-            }
-            break;
-          }
-          const uint32_t l = (uint32_t)__builtin_ctz(ok);
-          if (lane == l) sp[p] = c;
-          p = (p + l) & (kSlots - 1);
-        }
-        // the next probe (of this op or the run's next) reads these slots
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-      }
+      const bool erased = erase_key(sp, row, key, lane, trip) != 0;
       if (lane == 0) a.st[op] = erased ? kStErased : (uint8_t)0;
     }
   }

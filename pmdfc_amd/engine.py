@@ -71,6 +71,15 @@ class CompactResult(C.Structure):
                 ("depth_after", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class EraseMatchingResult(C.Structure):
+    """pmdfc_erase_matching_result_t"""
+    _fields_ = [("removed", C.c_uint64), ("segments_scanned", C.c_uint32), ("segments_changed", C.c_uint32),
+                ("segments_cleared", C.c_uint32)]
+
+
+MATCH_MAX = 1024  # PMDFC_MATCH_MAX
+INODE_MASK = 0xFFFFFFFF00000000  # the inode half of a cleancache key (inode << 32 | page index)
+
 # every symbol include/pmdfc_cceh.h declares (checked by tests/test_capi.py)
 EXPORTS = [
     "pmdfc_depth_for_hybrid", "pmdfc_depth_for_src", "pmdfc_abi_version", "pmdfc_last_error",
@@ -98,6 +107,7 @@ EXPORTS = [
     "pmdfc_cbf_rebuild", "pmdfc_cbf_audit",
     "pmdfc_cceh_erase",
     "pmdfc_cceh_compact", "pmdfc_cceh_compact_timing",
+    "pmdfc_cceh_erase_matching",
 ]
 
 
@@ -200,6 +210,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         "pmdfc_cceh_erase": (i32, [P, P, P, u64, P]),
         "pmdfc_cceh_compact": (i32, [P, u32, C.POINTER(CompactResult), P]),
         "pmdfc_cceh_compact_timing": (i32, [P, P, u32, C.POINTER(u32)]),
+        "pmdfc_cceh_erase_matching": (i32, [P, u64, P, u32, C.POINTER(EraseMatchingResult), P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -506,6 +517,23 @@ class CCEH:
             _check(load_library().pmdfc_cceh_erase(self._h, k[off:].data_ptr(), st[off:].data_ptr(), m,
                                                    self._d.stream()), "pmdfc_cceh_erase")
         return st if dev_in else _host_out(st, "u8")
+
+    def EraseMatching(self, patterns, mask: int = INODE_MASK) -> dict:
+        """Remove every stored entry whose key k has (k & mask) == (p & mask)
+        for one of the patterns p, with every copy of its key, in one scan of
+        the table (pmdfc_cceh_erase_matching).  The default
+        mask is the inode half of a cleancache key, so EraseMatching([ino << 32])
+        is invalidate_inode; mask 0 with any pattern empties the table.  At
+        most MATCH_MAX patterns (PmdfcError beyond); none removes nothing.  The
+        table afterwards is the table before with Erase of each matching key
+        applied.  Returns removed (entries, every copy counted),
+        segments_scanned, segments_changed and segments_cleared.  Synchronous."""
+        p = self._d.u64(patterns)
+        r = EraseMatchingResult()
+        _check(load_library().pmdfc_cceh_erase_matching(self._h, mask & 0xFFFFFFFFFFFFFFFF,
+                                                        p.data_ptr() if p.numel() else None, p.numel(),
+                                                        C.byref(r), self._d.stream()), "pmdfc_cceh_erase_matching")
+        return {n: getattr(r, n) for n, _ in EraseMatchingResult._fields_}
 
     def Compact(self, fill_limit: int = 512) -> dict:
         """Merge sibling segments that hold at most fill_limit entries together

@@ -195,6 +195,7 @@ void BatchCore::release() {
   if (sync_) (void)hipStreamSynchronize((hipStream_t)sync_);
   if (fa_dev_) (void)hipFree(fa_dev_);
   if (er_dev_) (void)hipFree(er_dev_);
+  if (em_dev_) (void)hipFree(em_dev_);
   if (fl_h_in_) (void)hipHostFree(fl_h_in_);
   if (fl_h_out_) (void)hipHostFree(fl_h_out_);
   if (fl_d_in_) (void)hipFree(fl_d_in_);
@@ -205,7 +206,7 @@ void BatchCore::release() {
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
   if (sync_) (void)hipStreamDestroy((hipStream_t)sync_);
   if (t_) pmdfc_cceh_destroy(t_);
-  fa_dev_ = nullptr, er_dev_ = nullptr, fl_h_in_ = fl_h_out_ = fl_d_in_ = fl_d_out_ = nullptr;
+  fa_dev_ = nullptr, er_dev_ = nullptr, em_dev_ = nullptr, fl_h_in_ = fl_h_out_ = fl_d_in_ = fl_d_out_ = nullptr;
   req_ = nullptr, resp_ = nullptr, ctl_ = nullptr, stream_ = sync_ = nullptr, t_ = nullptr;
 }
 
@@ -1079,6 +1080,34 @@ uint8_t BatchCore::Erase(uint64_t key) {
   uint8_t st = kBatchFailed;
   EraseRun(&key, &st, 1);
   return st;
+}
+
+int BatchCore::EraseMatching(uint64_t mask, const uint64_t* patterns, uint32_t n, pmdfc_erase_matching_result_t* out) {
+  if (n > PMDFC_MATCH_MAX || (n && !patterns)) return PMDFC_ERR_ARG;
+  pmdfc_erase_matching_result_t r{};
+  int rc = PMDFC_ERR_STATE;
+  if (!with_engine([&](hipStream_t st) {
+        if (!em_dev_ && hipMalloc((void**)&em_dev_, PMDFC_MATCH_MAX * sizeof(uint64_t)) != hipSuccess) {
+          em_dev_ = nullptr;
+          rc = PMDFC_ERR_NOMEM;
+          set_error("EraseMatching: out of device memory");
+          return;
+        }
+        if (n && hipMemcpyAsync(em_dev_, patterns, n * sizeof(uint64_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+          rc = PMDFC_ERR_HIP;
+          set_error("EraseMatching: HIP call failed");
+          return;
+        }
+        rc = pmdfc_cceh_erase_matching(t_, mask, em_dev_, n, &r, st);
+        if (rc != PMDFC_OK) {
+          set_error(std::string("EraseMatching: ") + pmdfc_last_error());
+          return;
+        }
+        if (r.removed && bf_) rc = rebuild_bf(st, nullptr);
+      }))
+    return PMDFC_ERR_STATE;
+  if (out) *out = r;
+  return rc;
 }
 
 int BatchCore::Compact(uint32_t fill_limit, pmdfc_compact_result_t* out) {

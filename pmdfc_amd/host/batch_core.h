@@ -38,8 +38,8 @@
 // post its reply from a completion) uses InsertAsync / GetAsync: the op is
 // queued and a callback runs on the control thread when its result is back.
 //
-// Calls that need the whole engine (Utilization, Capacity, FindAnyway, Erase
-// and EraseRun, Compact, the counting-BF pack, attach, rebuild and audit, Save and
+// Calls that need the whole engine (Utilization, Capacity, FindAnyway, Erase,
+// EraseRun and EraseMatching, Compact, the counting-BF pack, attach, rebuild and audit, Save and
 // Load) wait for every
 // op queued before them, stop the device wave, run on the engine's stream,
 // and start it again.
@@ -166,6 +166,16 @@ class BatchCore {
   // keys answered kBatchFailed.
   uint8_t Erase(uint64_t key);
   uint64_t EraseRun(const uint64_t* keys, uint8_t* status, uint64_t n);
+
+  // ---- pmdfc_cceh_erase_matching: every stored key k with (k & mask) ==
+  // (patterns[i] & mask) for some i < n <= PMDFC_MATCH_MAX goes, in one scan
+  // (DESIGN.md 4.10); patterns is host memory.  A whole-engine call like
+  // EraseRun: after every op enqueued so far, the waves stopped.  When it
+  // removed something and a counting BF is attached, the filter is rebuilt
+  // from the table and packed under the same stop (rebuild_bf), which is exact
+  // where EraseRun's per-key deletes leave the extra counts of duplicates.
+  // PMDFC_ERR_STATE from a completion callback (nothing done).  out nullable.
+  int EraseMatching(uint64_t mask, const uint64_t* patterns, uint32_t n, pmdfc_erase_matching_result_t* out);
 
   // ---- pmdfc_cceh_compact: sibling segments that fit one segment merged to
   // the fixpoint, their ids back in the arena.  A whole-engine
@@ -358,6 +368,7 @@ class BatchCore {
   uint64_t* fa_dev_ = nullptr;    // FindAnyway: device {key, value, status}
   uint8_t* er_dev_ = nullptr;     // EraseRun (allocated by the first): keys, the erased keys, statuses, the filter's answers
   uint64_t er_cap_ = 0;           // keys per engine batch
+  uint64_t* em_dev_ = nullptr;    // EraseMatching (allocated by the first): PMDFC_MATCH_MAX patterns
   // flood batches: pinned staging (keys, values, ops, cbf ops | values, statuses) and device copies
   uint64_t fl_cap_ = 0;
   uint8_t *fl_h_in_ = nullptr, *fl_h_out_ = nullptr, *fl_d_in_ = nullptr, *fl_d_out_ = nullptr;

@@ -60,6 +60,12 @@ class GpuCCEHHybrid : public ICCEH {
   int EraseBatch(const uint64_t* keys, uint8_t* status, uint64_t n) {
     return core_.EraseRun(keys, status, n) ? PMDFC_ERR_STATE : PMDFC_OK;
   }
+  // Every stored key k with (k & mask) == (patterns[i] & mask) for some i < n
+  // goes (BatchCore::EraseMatching; n <= PMDFC_MATCH_MAX, patterns in host
+  // memory): what invalidate_inode and invalidate_fs need.  result nullable.
+  int EraseMatching(uint64_t mask, const uint64_t* patterns, uint32_t n, pmdfc_erase_matching_result_t* result) {
+    return core_.EraseMatching(mask, patterns, n, result);
+  }
   // Sibling segments that fit one segment merged, their ids back in the arena
   // (BatchCore::Compact, pmdfc_cceh_compact); every stored pair stays.
   int Compact(uint32_t fill_limit, pmdfc_compact_result_t* out) { return core_.Compact(fill_limit, out); }

@@ -124,6 +124,12 @@ int64_t pmdfc_kv_erase_run(pmdfc_kv_t* kv, const uint64_t* keys, uint8_t* status
   return (int64_t)kv->core->EraseRun(keys, status, n);
 }
 
+int pmdfc_kv_erase_matching(pmdfc_kv_t* kv, uint64_t mask, const uint64_t* patterns, uint32_t n,
+                            pmdfc_erase_matching_result_t* out) {
+  if (!kv) return PMDFC_ERR_ARG;
+  return kv->core->EraseMatching(mask, patterns, n, out);
+}
+
 int pmdfc_kv_compact(pmdfc_kv_t* kv, uint32_t fill_limit, pmdfc_compact_result_t* out) {
   if (!kv || !out) return PMDFC_ERR_ARG;
   return kv->core->Compact(fill_limit, out);

@@ -19,7 +19,7 @@ import os
 
 import numpy as np
 
-from .engine import OP_GET, OP_INSERT, PMDFC_ERR_SIZE, ST_HIT, CompactResult, PmdfcError, Stats, _require_gpu, depth_for_hybrid, depth_for_src, load_library
+from .engine import OP_GET, OP_INSERT, PMDFC_ERR_SIZE, ST_HIT, INODE_MASK, MATCH_MAX, CompactResult, EraseMatchingResult, PmdfcError, Stats, _require_gpu, depth_for_hybrid, depth_for_src, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 KV_LIB_PATH = os.path.join(_HERE, "lib", "libpmdfc_gpucceh.so")
@@ -33,6 +33,7 @@ KV_EXPORTS = [
     "pmdfc_kv_create_error", "pmdfc_kv_save", "pmdfc_kv_save_packed", "pmdfc_kv_load",
     "pmdfc_kv_attach_cbf", "pmdfc_kv_rebuild_cbf", "pmdfc_kv_audit_cbf",
     "pmdfc_kv_erase", "pmdfc_kv_erase_run", "pmdfc_kv_compact",
+    "pmdfc_kv_erase_matching",
 ]
 
 _kvlib = None
@@ -79,6 +80,7 @@ def load_kv_library(path: str = KV_LIB_PATH) -> C.CDLL:
         "pmdfc_kv_erase": (i32, [P, u64, P]),
         "pmdfc_kv_erase_run": (i64, [P, P, P, u64]),
         "pmdfc_kv_compact": (i32, [P, u32, C.POINTER(CompactResult)]),
+        "pmdfc_kv_erase_matching": (i32, [P, u64, P, u32, C.POINTER(EraseMatchingResult)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -221,6 +223,32 @@ class KV:
         if rc < 0:
             self._err("erase_run", rc)
         return st
+
+    def erase_matching(self, patterns, mask: int = INODE_MASK) -> dict:
+        """CCEH.EraseMatching after every queued op, with the serving waves
+        stopped -> its counts: every stored key k with (k & mask) == (p & mask)
+        for one of the (at most MATCH_MAX) patterns goes.  An attached counting
+        BF is rebuilt from the table when something was removed."""
+        p = np.ascontiguousarray(patterns, dtype=np.uint64)
+        r = EraseMatchingResult()
+        rc = load_kv_library().pmdfc_kv_erase_matching(self._h, mask & 0xFFFFFFFFFFFFFFFF, p.ctypes.data, p.size,
+                                                       C.byref(r))
+        if rc != 0:
+            self._err("erase_matching", rc)
+        return {n: getattr(r, n) for n, _ in EraseMatchingResult._fields_}
+
+    def invalidate_inodes(self, inodes) -> dict:
+        """cleancache's invalidate_inode for every inode number given: keys are
+        inode << 32 | page index, so erase_matching of inode << 32 under the
+        inode mask, MATCH_MAX inodes per call -> the counts summed (above
+        MATCH_MAX inodes a segment that two calls change or clear is counted
+        by each; segments_scanned is the largest of the calls')."""
+        pats = np.ascontiguousarray(inodes, dtype=np.uint64) << np.uint64(32)
+        total = {n: 0 for n, _ in EraseMatchingResult._fields_}
+        for lo in range(0, pats.size, MATCH_MAX):
+            for n, v in self.erase_matching(pats[lo:lo + MATCH_MAX], INODE_MASK).items():
+                total[n] = max(total[n], v) if n == "segments_scanned" else total[n] + v
+        return total
 
     def compact(self, fill_limit: int = 512) -> dict:
         """CCEH.Compact after every queued op, with the serving waves stopped
