@@ -429,6 +429,41 @@ void oc_erase_batch(oc_cceh* t, const uint64_t* keys, size_t n, uint8_t* out_sta
   for (size_t i = 0; i < n; ++i) out_status[i] = (uint8_t)oc_erase(t, keys[i]);
 }
 
+/* Load  the inverse of oc_dump (the table after a Compact is
+ * the model's image): segment i of the dump becomes segment i, and the
+ * directory follows from the local depths.  No reference line to cite. */
+int oc_load(oc_cceh* t, uint32_t depth, uint32_t nseg, const uint32_t* local_depth,
+            const uint64_t* keys, const uint64_t* values) {
+  if (depth < 1 || depth > OC_MAX_DEPTH || nseg < 1) return -1;
+  uint64_t n = 1ULL << depth, x = 0;
+  for (uint32_t i = 0; i < nseg; ++i) { /* the segments tile the directory exactly */
+    uint32_t ld = local_depth[i];
+    if (ld < 1 || ld > depth) return -1;
+    uint64_t span = 1ULL << (depth - ld);
+    if (x >= n || (x & (span - 1)) != 0) return -1;
+    x += span;
+  }
+  if (x != n) return -1;
+  reserve_segments(t, nseg);
+  uint32_t* nd = (uint32_t*)malloc((size_t)n * sizeof(uint32_t));
+  x = 0;
+  for (uint32_t i = 0; i < nseg; ++i) {
+    oc_pair* seg = seg_ptr(t, i);
+    for (uint32_t j = 0; j < OC_SLOTS_PER_SEGMENT; ++j) {
+      size_t o = (size_t)i * OC_SLOTS_PER_SEGMENT + j;
+      seg[j].key = keys[o];
+      seg[j].value = keys[o] == OC_INVALID ? 0 : values[o];
+    }
+    t->ldepth[i] = local_depth[i];
+    for (uint64_t span = 1ULL << (depth - local_depth[i]); span; --span) nd[x++] = i;
+  }
+  free(t->dir);
+  t->dir = nd;
+  t->depth = depth;
+  t->nsegs = nseg;
+  return 0;
+}
+
 uint32_t oc_depth(const oc_cceh* t) { return t->depth; }
 uint32_t oc_num_segments(const oc_cceh* t) { return t->nsegs; }
 void oc_get_stats(const oc_cceh* t, oc_stats* out) { *out = t->st; }

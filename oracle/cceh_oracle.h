@@ -121,6 +121,22 @@ uint64_t oc_capacity(const oc_cceh* t);    /* CCEH_hybrid.cpp:429-435 */
 void oc_dump(const oc_cceh* t, uint32_t* dir_canon, uint32_t* local_depth,
              uint64_t* prefix, uint64_t* keys, uint64_t* values);
 
+/* Load: start from a canonical dump.  The table's segments and directory are
+ * replaced by those of the dump: nseg segments in directory order with their
+ * local depths, keys/values nseg*1024 each as oc_dump writes them; the
+ * directory of 2^depth entries is rebuilt from the local depths.  The reference
+ * never loads a table and never merges segments, so this cites the rule, not a
+ * reference line: Compact answers with a table image, which
+ * tests/compact_ref.py models, and the oracle goes on from that image.  It
+ * exists so that the serial oracle can follow a script across a Compact
+ * (tests/churn_ref.py); tests/test_churn_ref.py holds load(dump()) to change
+ * nothing.  The upsert mode and every counter of oc_stats stay as they are.
+ * Returns 0, or -1 with the table untouched unless 1 <= depth <= OC_MAX_DEPTH,
+ * 1 <= local_depth[i] <= depth for every segment and the segments tile the
+ * 2^depth directory exactly (each aligned to its own stride). */
+int oc_load(oc_cceh* t, uint32_t depth, uint32_t nseg, const uint32_t* local_depth,
+            const uint64_t* keys, const uint64_t* values);
+
 /* ---- bloom filter (client/bloom_filter.c:61-117; MSB-first u64 words) --- */
 void oc_bloom_add(uint64_t* bitmap, uint64_t nbits, uint32_t k, uint64_t key);
 int oc_bloom_check(const uint64_t* bitmap, uint64_t nbits, uint32_t k, uint64_t key,

@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
         L.oc_erase.restype = C.c_int
         L.oc_erase.argtypes = [P, C.c_uint64]
         L.oc_erase_batch.argtypes = [P, u64p, C.c_size_t, u8p]
+        L.oc_load.restype = C.c_int
+        L.oc_load.argtypes = [P, C.c_uint32, C.c_uint32, u32p, u64p, u64p]
         L.oc_depth.restype = C.c_uint32
         L.oc_depth.argtypes = [P]
         L.oc_num_segments.restype = C.c_uint32
@@ -214,6 +216,19 @@ class OracleCCEH:
         st = np.empty(keys.size, dtype=np.uint8)
         lib().oc_erase_batch(self._t, keys, keys.size, st)
         return st
+
+    def load(self, dump: dict) -> None:
+        """Start from a canonical dump (dump()'s dict, or any dict with depth,
+        local_depth, keys and values in directory order): oc_load.  upsert and
+        the counters of stats() stay.  ValueError, the table untouched, unless
+        the local depths tile the 2^depth directory exactly."""
+        ld = np.ascontiguousarray(dump["local_depth"], dtype=np.uint32)
+        keys = np.ascontiguousarray(dump["keys"], dtype=np.uint64)
+        vals = np.ascontiguousarray(dump["values"], dtype=np.uint64)
+        if keys.size != ld.size * 1024 or vals.size != keys.size:
+            raise ValueError("dump arrays do not match the segment count")
+        if lib().oc_load(self._t, int(dump["depth"]), ld.size, ld, keys, vals) != 0:
+            raise ValueError("the local depths do not tile the directory")
 
     @property
     def depth(self) -> int:

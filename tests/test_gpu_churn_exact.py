@@ -86,11 +86,46 @@ def apply_mixed(t, path, ops, keys, vals, cut):
     return vo, st
 
 
-def replay(t, s, cut, path, first=0, loss0=0):
+COMPACT_COUNTS = ("segments_before", "segments_after", "merges", "refused", "rounds", "depth_before", "depth_after")
+
+
+def match_step(t, s, r, i, what, loss0=0):
+    """Step i of script s, ("match", mask, patterns), through EraseMatching:
+    the result's four fields and the table are the model's and the oracle's."""
+    got = t.EraseMatching(s.steps[i][2], s.steps[i][1])
+    assert got == r.results[i], (what, got, r.results[i])
+    check_state(t, r.post[i], r.marks[i], what, loss0)
+
+
+def compact_step(t, s, r, i, what, loss0=0):
+    """Step i of script s, ("compact", fill_limit), through Compact -> the
+    loss0 that holds from here on.  The counts are the model's and the table
+    is the image the oracle went on from.  After a merge the engine was
+    rebuilt as restore() rebuilds one: its history counters restarted, so its
+    split_loss counts from the oracle's value at this step, and its bucket
+    resolution is what the image's shallowest segment allows.  With no merge
+    nothing restarted."""
+    res, before = r.results[i], t.stats()
+    got = t.Compact(s.steps[i][1])
+    assert {k: got[k] for k in COMPACT_COUNTS} == {k: res[k] for k in COMPACT_COUNTS}, (what, got, res)
+    after = t.stats()
+    if res["merges"] > 0:
+        assert after["splits"] == 0 and after["error_flags"] == 0, (what, after)
+        loss0 = r.marks[i]["split_loss"]
+    else:
+        assert after == before, (what, before, after)
+    check_state(t, r.post[i], r.marks[i], what, loss0)
+    assert after["bucket_bits"] == min(FULL_BITS, int(np.min(r.post[i]["local_depth"]))), (what, after["bucket_bits"])
+    return loss0
+
+
+def replay(t, s, cut, path, first=0, loss0=0, trace=None):
     """Steps first.. of script s on engine t: each mixed step in pieces of
     `cut` ops (0: whole) through `path`, each erase step through Erase in
-    pieces of `cut`.  Everything is compared with run_oracle(s).  Returns the
-    oracle's run and the engine's bucket_bits at every erase step."""
+    pieces of `cut`, a match step through EraseMatching, a compact step
+    through Compact.  Everything is compared with run_oracle(s).  Returns the
+    oracle's run and the engine's bucket_bits at every erase step; trace, a
+    list, receives (step, kind, bucket_bits after it) of every step."""
     r = CR.run_oracle(s)
     bits = []
     for i in range(first, len(s.steps)):
@@ -99,11 +134,17 @@ def replay(t, s, cut, path, first=0, loss0=0):
             vo, st = apply_mixed(t, path, step[1], step[2], step[3], cut)
             _eq(st, r.results[i][1], what + ("status",))
             _eq(vo, r.results[i][0], what + ("values",))
+        elif step[0] == "match":
+            match_step(t, s, r, i, what, loss0)
+        elif step[0] == "compact":
+            loss0 = compact_step(t, s, r, i, what, loss0)
         else:
             st = np.concatenate([t.Erase(step[1][a:b]) for a, b in _pieces(len(step[1]), cut)])
             _eq(st, r.results[i], what + ("erase status",))
             check_state(t, r.post[i], r.marks[i], what, loss0)
             bits.append(t.stats()["bucket_bits"])
+        if trace is not None:
+            trace.append((i, step[0], t.stats()["bucket_bits"]))
     check_state(t, r.final, r.marks[len(s.steps)], (s.name, path, cut, "end"), loss0)
     return r, bits
 
